@@ -23,6 +23,12 @@ columns split over the ranks (config C: one 8-SB tile column per GPU at
 N = 8); after every frame the ranks all-gather the reconstruction over RCCL
 (rv_replay_frame).  `value` = frames of the stream / max-over-ranks time
 ("scaling": "strong").  --config picks the other BASELINE shapes.
+
+A plain run sets up, warms up, times the steps and prints the result line.
+--full adds what takes runs of its own: the CPU baseline with the full-size
+parity pass ("cpu_baseline", "parity", "gpu_vs_cpu") and the emulated N-rank
+split ("emulated_ranks").  --dump-outputs DIR writes what the last timed
+step returned as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -460,6 +466,43 @@ def emulate_ranks(n, W, H, xdec, ydec, bd, nref, tiling, flags, gops=6, imp_wind
                       "launch), device-copy all-gather; each rank codes its frames serially"}
 
 
+# --dump-outputs stays under 64 MB: 16 bytes per result word, 4 per sample
+DUMP_WORD_SAMPLES = 600_000
+DUMP_RECON_SAMPLES = 12_500_000
+
+
+def _dump_sample(a, cap):
+    """`a`, or above `cap` elements a seeded sample of that many, in index
+    order (the same elements on every run)."""
+    if a.size <= cap:
+        return a
+    return a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+
+
+def dump_outputs(path, words, ent_stats, recon):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, as float arrays that carry the integers exactly.
+    result_words.npy  f64 [n, 2]: the (low, high) 32-bit halves of the u64
+                      words results() returned (timed_run's `words`; above
+                      DUMP_WORD_SAMPLES words a sample of that many);
+    entropy.npy       f64 [6]: entropy_stats() -- the last frame's
+                      coefficient bytes, tiles, its byte hash's (low, high)
+                      halves, frames coded, bytes over every frame (with F8);
+    recon.npy         f32: the reconstruction of the last coded frame (planar
+                      Y, U, V as get_recon returns it; above
+                      DUMP_RECON_SAMPLES samples a sample of that many)."""
+    os.makedirs(path, exist_ok=True)
+    w = _dump_sample(np.asarray(words, dtype=np.uint64), DUMP_WORD_SAMPLES)
+    np.save(os.path.join(path, "result_words.npy"),
+            np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64))
+    if ent_stats is not None:
+        e = [int(v) for v in ent_stats]
+        np.save(os.path.join(path, "entropy.npy"),
+                np.array([e[0], e[1], e[2] & 0xFFFFFFFF, e[2] >> 32, e[3], e[4]], dtype=np.float64))
+    np.save(os.path.join(path, "recon.npy"),
+            _dump_sample(recon, DUMP_RECON_SAMPLES).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -469,6 +512,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="2160p", choices=sorted(CONFIGS))
     ap.add_argument("--refs", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline "
+                         "with the full-size parity pass (--cpu-seconds, --no-cpu-baseline) and "
+                         "the emulated N-rank split (--emulate-ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--speed", type=int, choices=(6, 10), default=None,
@@ -482,8 +532,9 @@ def main():
                          "off with several ranks) -- the default; 'cdef' / 'deblock' / 'none' "
                          "for A/B")
     ap.add_argument("--emulate-ranks", type=int, default=8,
-                    help="N > 1 (single-GPU runs): also code the N-rank tile-group split as N "
-                         "replays on this GPU and report the projected N-rank step (0: off)")
+                    help="with --full, N > 1 (single-GPU runs): also code the N-rank tile-group "
+                         "split as N replays on this GPU and report the projected N-rank step "
+                         "(0: off)")
     ap.add_argument("--serial-levels", action="store_true",
                     help="one instance codes every frame (default on one GPU: the level-2 "
                          "frames run on a twin instance concurrently with levels 0 / 1)")
@@ -593,6 +644,10 @@ def main():
     if os.environ.get("RAV1E_HIP_RDO_PHASES") == "1":  # diagnostic: the rounds' F4 phases
         R._check(R.lib().rv_rdo_phase_dump(), "rv_rdo_phase_dump")
     ent_stats = eng.entropy_stats() if ent else None
+    if args.dump_outputs and rank == 0 and args.warmup + args.steps > 0:
+        last = RP.frame_info(args.warmup + args.steps - 1, nref)["display"]
+        dump_outputs(args.dump_outputs, words, ent_stats, hip.get_recon(last))
+        progress(f"outputs of the last timed frame (display {last}) written")
 
     # per-kernel times over the instrumented frames of the timed region
     nonkey = range(args.warmup - 1, args.warmup - 1 + args.steps)
@@ -857,12 +912,12 @@ def main():
 
     emu = None
     n_emu = min(args.emulate_ranks, tiling["cols"] * tiling["rows"])  # one tile group per rank
-    if rank == 0 and world == 1 and n_emu > 1:
+    if args.full and rank == 0 and world == 1 and n_emu > 1:
         emu = emulate_ranks(n_emu, W, H, xdec, ydec, bd, nref, tiling, flags,
                             imp_window=imp_window, pj=pj)
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the CPU codes the same frames: the GPU's inputs, downloaded
         inputs = [hip.get_input(i) for i in range(min(22 + imp_window, n_inputs))]
         if paired:

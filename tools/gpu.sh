@@ -28,7 +28,7 @@ case "$MODE" in
     exec bash "$R/tools/gpu_step.sh" \
       "900 $TAG/pytest_gpu.log $PYT" \
       "300 $TAG/smoke.log python -c 'import __graft_entry__ as g; g.smoke()'" \
-      "400 $TAG/bench_default.log python $R/bench.py" ;;
+      "400 $TAG/bench_default.log python $R/bench.py --full" ;;
   tests)
     exec bash "$R/tools/gpu_step.sh" "900 $TAG/pytest_k.log $PYT -v -k '$1'" ;;
   testbench)
@@ -36,13 +36,13 @@ case "$MODE" in
     # config, in one step chain (a crash stops it; a test failure does not)
     expr=$1; shift
     steps=("900 $TAG/pytest_k.log $PYT -v -k '$expr'")
-    for c in "$@"; do steps+=("400 $TAG/bench_$c.log python $R/bench.py --config $c"); done
+    for c in "$@"; do steps+=("400 $TAG/bench_$c.log python $R/bench.py --full --config $c"); done
     exec bash "$R/tools/gpu_step.sh" "${steps[@]}" ;;
   bench)
     cfgs=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do cfgs+=("$1"); shift; done
     [ "$1" = "--" ] && shift
     steps=()
-    for c in "${cfgs[@]}"; do steps+=("400 $TAG/bench_$c.log python $R/bench.py --config $c $*"); done
+    for c in "${cfgs[@]}"; do steps+=("400 $TAG/bench_$c.log python $R/bench.py --full --config $c $*"); done
     exec bash "$R/tools/gpu_step.sh" "${steps[@]}" ;;
   prof)
     CFG=${1:-2160p}; shift
