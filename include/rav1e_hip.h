@@ -312,6 +312,56 @@ typedef struct rv_intra_job {
 int rv_predict_intra_batch(const rv_plane *dst, const rv_intra_job *d_jobs, const void *d_edges,
                            int n, int tx_size, int bit_depth, void *stream);
 
+/* ---- chroma from luma (src/encoder.rs:1714-1755, src/predict.rs:836-892,
+ * src/rdo.rs:1261-1336) ---------------------------------------------------
+ * A job names a partition by its luma pixel position (4 * tile_bo, relative
+ * to the planes' pixel (0, 0)); the chroma block lies at (bo >> dec) << 2
+ * per axis (plane_offset / Area::BlockStartingAt).  variant: the
+ * PredictionVariant of the chroma block (bit 0 a left column, bit 1 an above
+ * row), read by the search only.  bsize is a BlockSize (src/partition.rs:
+ * 116-140).  RV_EINVAL, without a launch, unless cfl_allowed() holds
+ * (bsize <= BLOCK_32X32, src/partition.rs:174-177) and subsampled_size(xdec,
+ * ydec) is valid (:245-286); the jobs being device data, has_chroma
+ * (src/context.rs:551-560) of each job is the caller's to assert.  Planes
+ * read in pixel runs (the luma plane, the source chroma planes) must have
+ * xorigin and stride multiples of 4 and a 16-byte aligned allocation, as
+ * rv_plane_geometry lays them out; RV_EINVAL otherwise. */
+typedef struct rv_cfl_job {
+  int32_t x, y;
+  int32_t variant;
+  int32_t reserved;
+} rv_cfl_job;
+/* luma_ac (src/encoder.rs:1714-1755) of every job: the W x H block
+ * (subsampled_size) of summed luma pixels << (3 - xdec - ydec) minus their
+ * rounded average, d_ac[i * W * H + r * W + c], i16.  For a sub-8x8 block
+ * the luma origin moves by sub8x8_offset (src/partition.rs:303-312).  Reads
+ * luma pixels only; a block may reach into the padding. */
+int rv_cfl_luma_ac_batch(const rv_plane *luma, const rv_cfl_job *d_jobs, int n, int bsize,
+                         int xdec, int ydec, int16_t *d_ac, void *stream);
+/* predict_intra(UV_CFL_PRED) (src/predict.rs:202-241: alpha == 0 is
+ * DC_PRED) = pred_cfl / _128 / _left / _top by the job's variant over
+ * pred_cfl_inner and get_scaled_luma_q0 (src/predict.rs:836-892, 485-493).
+ * d_jobs: rv_intra_job with mode 13 (UV_CFL_PRED); d_edges as for
+ * rv_predict_intra_batch; d_ac: [n][W * H] i16 with row stride W; d_alpha:
+ * [n] i16.  RV_ENOTSUP for the 64-point TxSizes (the reference asserts
+ * 32 >= W, src/predict.rs:843). */
+int rv_predict_cfl_batch(const rv_plane *dst, const rv_intra_job *d_jobs, const void *d_edges,
+                         const int16_t *d_ac, const int16_t *d_alpha, int n, int tx_size,
+                         int bit_depth, void *stream);
+/* rdo_cfl_alpha (src/rdo.rs:1261-1336), fused: luma_ac of rec[0], and per
+ * chroma plane the DC of the reconstructed neighbours the variant allows
+ * (get_intra_edges(.., Some(UV_CFL_PRED)), src/partition.rs:542-595), the
+ * sse_wxh (bias 1, src/rdo.rs:286-335) of src against the prediction for the
+ * alphas -16 .. 16, and the reference's scan with its early break (:1311-
+ * 1327).  rec, src: the three planes of the reconstruction and the source;
+ * xdec / ydec are those of rec[1].  d_alpha[i * 2 + p]: the alpha the scan
+ * returns for U (p = 0) and V (1); d_cost (may be NULL): the SSE at that
+ * alpha.  The reference leaves the last tried prediction in rec, which the
+ * encoder overwrites at once; rec is left untouched here. */
+int rv_cfl_alpha_search_batch(const rv_plane *rec, const rv_plane *src, const rv_cfl_job *d_jobs,
+                              int n, int bsize, int bit_depth, int16_t *d_alpha,
+                              uint64_t *d_cost, void *stream);
+
 /* ---- deblocking (src/deblock.rs) ---------------------------------------
  * deblock_plane (src/deblock.rs:1174-1335, replaces the per-edge loop of
  * deblock_filter_frame :1410-1416) of plane pli (0 Y, 1 U, 2 V) of a frame

@@ -51,6 +51,7 @@ class RvFsResult(C.Structure):
 # job layouts as numpy dtypes (arrays of these go to the device verbatim)
 DIST_JOB = np.dtype([("org_x", "<i4"), ("org_y", "<i4"), ("ref_x", "<i4"), ("ref_y", "<i4")])
 INTRA_JOB = np.dtype([("x", "<i4"), ("y", "<i4"), ("mode", "<i4"), ("variant", "<i4")])
+CFL_JOB = np.dtype([("x", "<i4"), ("y", "<i4"), ("variant", "<i4"), ("reserved", "<i4")])
 MC_JOB = np.dtype([("src_x", "<i4"), ("src_y", "<i4"), ("dst_x", "<i4"), ("dst_y", "<i4"),
                    ("col_frac", "<i4"), ("row_frac", "<i4")])
 MOTION_VECTOR = np.dtype([("row", "<i2"), ("col", "<i2")])  # rv_mv / MotionVector
@@ -252,6 +253,9 @@ def _declare(L):
         "rv_cdef_moments_batch": (i32, [P, P, vp, i32, i32, i32, vp, vp]),
         "rv_put_8tap_batch": (i32, [P, P, vp, i32, i32, i32, i32, i32, i32, vp]),
         "rv_predict_intra_batch": (i32, [P, vp, vp, i32, i32, i32, vp]),
+        "rv_cfl_luma_ac_batch": (i32, [P, vp, i32, i32, i32, i32, vp, vp]),
+        "rv_predict_cfl_batch": (i32, [P, vp, vp, vp, vp, i32, i32, i32, vp]),
+        "rv_cfl_alpha_search_batch": (i32, [P, P, vp, i32, i32, i32, vp, vp, vp]),
         "rv_deblock_plane": (i32, [P, i32, i32, i32, vp, vp, i32, vp, i32, vp]),
         "rv_deblock_fast_level": (i32, [i32, i32, i32]),
         "rv_deblock_sse": (i32, [P, P, i32, i32, vp, vp, i32, vp, vp, i32, vp]),
@@ -578,6 +582,7 @@ class PredictionMode(enum.IntEnum):
     SMOOTH_V_PRED = 10
     SMOOTH_H_PRED = 11
     PAETH_PRED = 12
+    UV_CFL_PRED = 13
 
 
 # RAV1E_INTRA_MODES (src/predict.rs:32-46): the screening order
@@ -599,6 +604,207 @@ def predict_intra_batch(dst: DevicePlane, jobs, edges: np.ndarray, tx_size, bit_
     _check(lib().rv_predict_intra_batch(C.byref(dst.desc), dj.ptr, de.ptr, len(jobs), tx_size,
                                         bit_depth, None), "rv_predict_intra_batch")
     _sync()
+
+
+# ---- chroma from luma (rv_cfl.hip) ------------------------------------------
+def cfl_allowed(bsize) -> bool:
+    """BlockSize::cfl_allowed (src/partition.rs:174-177): enum order."""
+    return 0 <= int(bsize) <= int(BlockSize.BLOCK_32X32)
+
+
+# the sizes subsampled_size maps to a valid one at 4:2:2
+_SS_422 = {"BLOCK_4X4", "BLOCK_8X4", "BLOCK_8X8", "BLOCK_16X4", "BLOCK_16X8", "BLOCK_16X16",
+           "BLOCK_32X8", "BLOCK_32X16", "BLOCK_32X32", "BLOCK_64X16", "BLOCK_64X32", "BLOCK_64X64",
+           "BLOCK_128X64", "BLOCK_128X128"}
+
+
+def subsampled_size(bsize, xdec, ydec):
+    """BlockSize::subsampled_size (src/partition.rs:245-286) as (w, h) of the
+    chroma-plane block, or None for BLOCK_INVALID."""
+    b = BlockSize(bsize)
+    w, h = b.width(), b.height()
+    if (xdec, ydec) == (0, 0):
+        return w, h
+    if (xdec, ydec) == (1, 0):
+        return (max(4, w // 2), h) if b.name in _SS_422 else None
+    if (xdec, ydec) == (1, 1):  # every size has one
+        return max(4, w // 2), max(4, h // 2)
+    raise Rav1eHipError("subsampled_size: 4:4:4, 4:2:2 or 4:2:0")
+
+
+def has_chroma(x, y, bsize, xdec, ydec):
+    """has_chroma (src/context.rs:551-560) of the block at luma pixel (x, y)."""
+    b = BlockSize(bsize)
+    bx, by = np.asarray(x) >> 2, np.asarray(y) >> 2
+    okx = ((bx & 1) == 1) | ((b.width() >> 2) & 1 == 0) | (xdec == 0)
+    oky = ((by & 1) == 1) | ((b.height() >> 2) & 1 == 0) | (ydec == 0)
+    return okx & oky
+
+
+def _cfl_geometry(who, bsize, xdec, ydec):
+    """(w, h) of the chroma block and the luma origin's sub8x8_offset in
+    pixels (src/partition.rs:303-312), or the argument error."""
+    if not cfl_allowed(bsize):
+        raise Rav1eHipError(f"{who}: CfL needs a block size up to BLOCK_32X32 (cfl_allowed)")
+    if (xdec, ydec) not in ((0, 0), (1, 0), (1, 1)):
+        raise Rav1eHipError(f"{who}: subsampling must be 4:4:4, 4:2:2 or 4:2:0")
+    wh = subsampled_size(bsize, xdec, ydec)
+    if wh is None:
+        raise Rav1eHipError(f"{who}: {BlockSize(bsize).name} has no subsampled size at "
+                            f"xdec {xdec}, ydec {ydec}")
+    b = BlockSize(bsize)
+    return wh, (-4 if xdec and b.width() == 4 else 0, -4 if ydec and b.height() == 4 else 0)
+
+
+def _cfl_jobs(who, jobs, bsize, xdec, ydec):
+    jobs = np.ascontiguousarray(jobs, dtype=CFL_JOB)
+    if ((jobs["x"] & 3) != 0).any() or ((jobs["y"] & 3) != 0).any() or \
+            (jobs["x"] < 0).any() or (jobs["y"] < 0).any():
+        raise Rav1eHipError(f"{who}: job positions are luma pixels of a block offset (4 * bo)")
+    if not np.all(has_chroma(jobs["x"], jobs["y"], bsize, xdec, ydec)):
+        raise Rav1eHipError(f"{who}: a job's block has no chroma (has_chroma)")
+    if ((jobs["variant"] < 0) | (jobs["variant"] > 3)).any():
+        raise Rav1eHipError(f"{who}: variant is a PredictionVariant (0 .. 3)")
+    return jobs
+
+
+def _inside(plane: DevicePlane, x0, y0, x1, y1) -> bool:
+    """Whether the pixel rectangles [x0, x1) x [y0, y1) (arrays, visible
+    coordinates) lie inside the plane's padded allocation."""
+    d = plane.desc
+    return bool(np.all(x0 >= -d.xorigin) and np.all(x1 <= d.stride - d.xorigin) and
+                np.all(y0 >= -d.yorigin) and np.all(y1 <= d.alloc_height - d.yorigin))
+
+
+def _cfl_run_plane(who, plane: DevicePlane):
+    """The planes rv_cfl.hip reads in aligned pixel runs."""
+    d = plane.desc
+    if d.xorigin & 3 or d.stride & 3 or (d.data or 0) & 15:
+        raise Rav1eHipError(f"{who}: xorigin and stride must be multiples of 4 and the "
+                            "allocation 16-byte aligned (rv_plane_geometry's layout)")
+
+
+def luma_ac_batch(luma: DevicePlane, jobs, bsize, xdec, ydec) -> np.ndarray:
+    """luma_ac (src/encoder.rs:1714-1755) of every job (CFL_JOB: the
+    partition's luma pixel position): (n, H, W) i16 over the chroma-plane
+    block W x H = bsize.subsampled_size(xdec, ydec)."""
+    (w, h), (ox, oy) = _cfl_geometry("luma_ac_batch", bsize, xdec, ydec)
+    jobs = _cfl_jobs("luma_ac_batch", jobs, bsize, xdec, ydec)
+    _cfl_run_plane("luma_ac_batch", luma)
+    lx, ly = jobs["x"] + ox, jobs["y"] + oy
+    if not _inside(luma, lx, ly, lx + (w << xdec), ly + (h << ydec)):
+        raise Rav1eHipError("luma_ac_batch: a luma block leaves the padded plane")
+    dj = DeviceBuffer.from_array(jobs)
+    out = DeviceBuffer(2 * w * h * max(1, len(jobs)))
+    _check(lib().rv_cfl_luma_ac_batch(C.byref(luma.desc), dj.ptr, len(jobs), int(bsize), xdec, ydec,
+                                      out.ptr, None), "rv_cfl_luma_ac_batch")
+    _sync()
+    return out.download(np.int16, w * h * len(jobs)).reshape(len(jobs), h, w)
+
+
+def predict_cfl_batch(dst: DevicePlane, jobs, edges: np.ndarray, ac: np.ndarray, alpha, tx_size,
+                      bit_depth=8):
+    """predict_intra(UV_CFL_PRED) (src/predict.rs:202-241, 836-892) of every
+    job (INTRA_JOB with mode 13) into dst: edges (n, 257) as for
+    predict_intra_batch, ac (n, H, W) i16, alpha (n,) in -16 .. 16."""
+    tx = TxSize(tx_size)
+    w, h = tx.width(), tx.height()
+    if w > 32 or h > 32:
+        raise Rav1eHipError("predict_cfl_batch: no CfL for 64-point transform sizes")
+    jobs = np.ascontiguousarray(jobs, dtype=INTRA_JOB)
+    n = len(jobs)
+    edges = np.ascontiguousarray(edges, dtype=np.uint16 if bit_depth > 8 else np.uint8)
+    if edges.shape != (n, EDGE_PX):
+        raise Rav1eHipError("predict_cfl_batch: edges must be (n_jobs, 257)")
+    ac = np.asarray(ac)
+    if ac.dtype != np.int16 or ac.shape != (n, h, w):
+        raise Rav1eHipError("predict_cfl_batch: ac must be int16 (n_jobs, H, W)")
+    ac = np.ascontiguousarray(ac)
+    alpha = np.asarray(alpha)
+    if alpha.shape != (n,) or (np.abs(alpha.astype(np.int64)) > 16).any():
+        raise Rav1eHipError("predict_cfl_batch: alpha must be (n_jobs,) in -16 .. 16")
+    alpha = np.ascontiguousarray(alpha, dtype=np.int16)
+    if not (jobs["mode"] == PredictionMode.UV_CFL_PRED).all():
+        raise Rav1eHipError("predict_cfl_batch: jobs must have mode UV_CFL_PRED")
+    if ((jobs["variant"] < 0) | (jobs["variant"] > 3)).any():
+        raise Rav1eHipError("predict_cfl_batch: variant is a PredictionVariant (0 .. 3)")
+    if not _inside(dst, jobs["x"], jobs["y"], jobs["x"] + w, jobs["y"] + h):
+        raise Rav1eHipError("predict_cfl_batch: a block leaves the padded plane")
+    dj, de = DeviceBuffer.from_array(jobs), DeviceBuffer.from_array(edges)
+    da, dl = DeviceBuffer.from_array(ac), DeviceBuffer.from_array(alpha)
+    _check(lib().rv_predict_cfl_batch(C.byref(dst.desc), dj.ptr, de.ptr, da.ptr, dl.ptr, n,
+                                      int(tx_size), bit_depth, None), "rv_predict_cfl_batch")
+    _sync()
+
+
+def cfl_alpha_search_batch(rec, src, jobs, bsize, bit_depth=8, with_cost=False):
+    """rdo_cfl_alpha (src/rdo.rs:1261-1336) of every job: rec / src = three
+    DevicePlanes each (Y, U, V; the reconstruction and the source), jobs
+    CFL_JOB (the partition's luma pixel position and the chroma block's
+    PredictionVariant).  Returns alpha (n, 2) i16 for U and V -- what the
+    reference's scan returns, not the argmin -- and, with_cost, the SSE at
+    that alpha (n, 2) u64.  rec is left untouched."""
+    if len(rec) != 3 or len(src) != 3:
+        raise Rav1eHipError("cfl_alpha_search_batch: rec / src are three planes each")
+    xdec, ydec = rec[1].desc.xdec, rec[1].desc.ydec
+    for p in (1, 2):
+        if (rec[p].desc.xdec, rec[p].desc.ydec, src[p].desc.xdec, src[p].desc.ydec) != \
+                (xdec, ydec, xdec, ydec):
+            raise Rav1eHipError("cfl_alpha_search_batch: chroma planes differ in subsampling")
+    (w, h), (ox, oy) = _cfl_geometry("cfl_alpha_search_batch", bsize, xdec, ydec)
+    jobs = _cfl_jobs("cfl_alpha_search_batch", jobs, bsize, xdec, ydec)
+    for p in (rec[0], src[1], src[2]):
+        _cfl_run_plane("cfl_alpha_search_batch", p)
+    lx, ly = jobs["x"] + ox, jobs["y"] + oy
+    cx, cy = ((jobs["x"] >> 2) >> xdec) << 2, ((jobs["y"] >> 2) >> ydec) << 2
+    left, top = jobs["variant"] & 1, (jobs["variant"] >> 1) & 1
+    if not _inside(rec[0], lx, ly, lx + (w << xdec), ly + (h << ydec)) or \
+            not all(_inside(rec[p], cx - left, cy - top, cx + w, cy + h) and
+                    _inside(src[p], cx, cy, cx + w, cy + h) for p in (1, 2)):
+        raise Rav1eHipError("cfl_alpha_search_batch: a block or its neighbours leave the padded "
+                            "plane")
+    n = len(jobs)
+    rp = (RvPlane * 3)(*(p.desc for p in rec))
+    sp = (RvPlane * 3)(*(p.desc for p in src))
+    dj = DeviceBuffer.from_array(jobs)
+    da = DeviceBuffer(4 * max(1, n))
+    dc = DeviceBuffer(16 * max(1, n)) if with_cost else None
+    _check(lib().rv_cfl_alpha_search_batch(rp, sp, dj.ptr, n, int(bsize), bit_depth, da.ptr,
+                                           dc.ptr if dc else None, None),
+           "rv_cfl_alpha_search_batch")
+    _sync()
+    alpha = da.download(np.int16, 2 * n).reshape(n, 2)
+    return (alpha, dc.download(np.uint64, 2 * n).reshape(n, 2)) if with_cost else alpha
+
+
+class CFLParams:
+    """CFLParams (src/context.rs:1866-1915): the joint sign and the two
+    magnitudes write_cfl_alphas codes.  CFLSign: 0 ZERO, 1 NEG, 2 POS."""
+    SIGN_ZERO, SIGN_NEG, SIGN_POS = 0, 1, 2
+    _SIGN_VALUE = (0, -1, 1)  # cfl_sign_value
+
+    def __init__(self, sign=(1, 0), scale=(1, 0)):  # Default: (NEG, ZERO), (1, 0)
+        self.sign, self.scale = tuple(sign), tuple(scale)
+
+    @classmethod
+    def from_alpha(cls, u: int, v: int) -> "CFLParams":
+        sg = lambda a: (cls.SIGN_NEG, cls.SIGN_ZERO, cls.SIGN_POS)[(a > 0) - (a < 0) + 1]
+        return cls((sg(u), sg(v)), (abs(int(u)), abs(int(v))))
+
+    def joint_sign(self) -> int:
+        assert self.sign[0] != self.SIGN_ZERO or self.sign[1] != self.SIGN_ZERO
+        return self.sign[0] * 3 + self.sign[1] - 1
+
+    def context(self, uv: int) -> int:
+        assert self.sign[uv] != self.SIGN_ZERO
+        return (self.sign[uv] - 1) * 3 + self.sign[1 - uv]
+
+    def index(self, uv: int) -> int:
+        assert self.sign[uv] != self.SIGN_ZERO and self.scale[uv] != 0
+        return self.scale[uv] - 1
+
+    def alpha(self, uv: int) -> int:
+        return self._SIGN_VALUE[self.sign[uv]] * self.scale[uv]
 
 
 def deblock_plane(plane: DevicePlane, pli, width, height, lg: np.ndarray, skip: np.ndarray,

@@ -1046,7 +1046,8 @@ def intra_env(I):
         I.globals.vars.setdefault(n, RI.StructType(n))
     trait = "pub trait Intra<T>: Dim"
     meths = ["pred_dc", "pred_dc_128", "pred_dc_left", "pred_dc_top", "pred_h", "pred_v",
-             "pred_paeth", "pred_smooth", "pred_smooth_h", "pred_smooth_v", "pred_directional"]
+             "pred_paeth", "pred_smooth", "pred_smooth_h", "pred_smooth_v", "pred_directional",
+             "pred_cfl_inner", "pred_cfl", "pred_cfl_128", "pred_cfl_left", "pred_cfl_top"]
     tfn = {m: I.make_fn(pr.fn(m, trait), I.globals) for m in meths}
     cache = {}
 
@@ -1055,7 +1056,8 @@ def intra_env(I):
             size = _NS(W=RI.TInt(w, "usize"), H=RI.TInt(h, "usize"))
             b = _NS(W=size.W, H=size.H)
             for m, f in tfn.items():
-                setattr(b, m, lambda *a, _f=f, _s=size: _f(*a, bind={"Self": _s, "T": PModeV.pixel}))
+                # Self is the block itself: pred_cfl* call Self::pred_dc* / Self::pred_cfl_inner
+                setattr(b, m, lambda *a, _f=f, _s=b: _f(*a, bind={"Self": _s, "T": PModeV.pixel}))
             cache[(w, h)] = b
         return cache[(w, h)]
     inner = I.make_fn(pr.fn("predict_intra_inner", "pub(crate) mod native"), I.globals)

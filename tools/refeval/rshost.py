@@ -198,6 +198,12 @@ def to_rect(area, xdec, ydec, parent_w, parent_h):
         return Struct("Rect", {"x": wrap(x, "isize"), "y": wrap(y, "isize"),
                                "width": wrap(parent_w - x, "usize"),
                                "height": wrap(parent_h - y, "usize")})
+    if kind == "BlockStartingAt":  # :91-100, BLOCK_TO_PLANE_SHIFT = 2
+        bo = f["bo"]
+        x, y = int(bo.x) >> int(xdec) << 2, int(bo.y) >> int(ydec) << 2
+        return Struct("Rect", {"x": wrap(x, "isize"), "y": wrap(y, "isize"),
+                               "width": wrap(parent_w - x, "usize"),
+                               "height": wrap(parent_h - y, "usize")})
     raise NotImplementedError("Area::" + kind)
 
 

@@ -1921,6 +1921,8 @@ def _iter_method(g, name, args, gty):
         return It(g)
     if name == "zip":
         return It(zip(g, to_iter(args[0])))
+    if name in ("len", "count"):  # ExactSizeIterator::len consumes nothing a caller reuses here
+        return TInt(sum(1 for _ in g), "usize")
     if name == "map":
         f = args[0]
         return It(f(x) for x in g)
