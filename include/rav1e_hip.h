@@ -362,6 +362,39 @@ int rv_cfl_alpha_search_batch(const rv_plane *rec, const rv_plane *src, const rv
                               int n, int bsize, int bit_depth, int16_t *d_alpha,
                               uint64_t *d_cost, void *stream);
 
+/* ---- scene-change detection (src/scenechange/mod.rs) ---------------------
+ * The frame-pair sums has_scenecut (:167-207) folds over Frame::iter()
+ * (PixelIter, src/frame/mod.rs:126-172), before its division by len: for
+ * every luma position (x, y) of [0, w) x [0, h) but the last one (w - 1,
+ * h - 1), which the iterator never yields, |a - b| of plane k at (x >> xdec,
+ * y >> ydec).  For a chroma plane that is a sum over its own pixels with the
+ * weight min(1 << xdec, w - (cx << xdec)) * min(1 << ydec, h - (cy << ydec)),
+ * one less at the pixel that holds the last luma position.  The `as u16`
+ * truncation, the division by w * h, the / 3 and the threshold are the
+ * caller's (rav1e_amd.SceneChangeDetector).
+ * frames: host array [n_frames][n_planes] of rv_plane, n_planes 1 (luma) or
+ * 3; pairs: host array of indices into frames; d_sums: device u64
+ * [n_pairs][n_planes], every entry written on `stream` (two launches: the
+ * pass over the pixels, which leaves per-workgroup partial sums in a slab the
+ * library keeps per calling thread and stream, and a one-workgroup pass that
+ * adds them up; integer sums, so the result does not depend on scheduling).
+ * Every frame's pixels are read once per call however many pairs name it;
+ * only the visible area is read, with no alignment requirement on it.  A
+ * pair with a == b gives 0.
+ * RV_EINVAL, without a launch, when n_frames is outside 2 ..
+ * RV_DELTA_MAX_FRAMES, n_pairs outside 1 .. RV_DELTA_MAX_PAIRS, n_planes not
+ * 1 or 3, a pair index out of range, the frames do not all share hbd and, per
+ * plane, size and decimation, the chroma decimation is not 4:4:4 / 4:2:2 /
+ * 4:2:0, or a chroma plane is not (w + xdec) >> xdec by (h + ydec) >> ydec. */
+typedef struct rv_delta_pair {
+  int32_t a, b;
+} rv_delta_pair;
+#define RV_DELTA_MAX_FRAMES 8
+#define RV_DELTA_MAX_PAIRS 16
+int rv_frame_delta_batch(const rv_plane *frames, int n_frames, int n_planes,
+                         const rv_delta_pair *pairs, int n_pairs, uint64_t *d_sums,
+                         void *stream);
+
 /* ---- deblocking (src/deblock.rs) ---------------------------------------
  * deblock_plane (src/deblock.rs:1174-1335, replaces the per-edge loop of
  * deblock_filter_frame :1410-1416) of plane pli (0 Y, 1 U, 2 V) of a frame

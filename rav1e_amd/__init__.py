@@ -256,6 +256,7 @@ def _declare(L):
         "rv_cfl_luma_ac_batch": (i32, [P, vp, i32, i32, i32, i32, vp, vp]),
         "rv_predict_cfl_batch": (i32, [P, vp, vp, vp, vp, i32, i32, i32, vp]),
         "rv_cfl_alpha_search_batch": (i32, [P, P, vp, i32, i32, i32, vp, vp, vp]),
+        "rv_frame_delta_batch": (i32, [P, i32, i32, vp, i32, vp, vp]),
         "rv_deblock_plane": (i32, [P, i32, i32, i32, vp, vp, i32, vp, i32, vp]),
         "rv_deblock_fast_level": (i32, [i32, i32, i32]),
         "rv_deblock_sse": (i32, [P, P, i32, i32, vp, vp, i32, vp, vp, i32, vp]),
@@ -805,6 +806,316 @@ class CFLParams:
 
     def alpha(self, uv: int) -> int:
         return self._SIGN_VALUE[self.sign[uv]] * self.scale[uv]
+
+
+# ---- scene-change detection (rv_scenecut.hip) -----------------------------------
+DELTA_MAX_FRAMES, DELTA_MAX_PAIRS = 8, 16  # RV_DELTA_MAX_FRAMES / _PAIRS
+
+
+def _delta_geometry(frames, pairs):
+    """The checks of rv_frame_delta_batch, on the descriptors alone; returns
+    (n_planes, pairs as int32 (n, 2))."""
+    who = "frame_deltas"
+    frames = [tuple(f) for f in frames]
+    if not 2 <= len(frames) <= DELTA_MAX_FRAMES:
+        raise Rav1eHipError(f"{who}: 2 .. {DELTA_MAX_FRAMES} frames, not {len(frames)}")
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if not 1 <= len(pairs) <= DELTA_MAX_PAIRS:
+        raise Rav1eHipError(f"{who}: 1 .. {DELTA_MAX_PAIRS} pairs, not {len(pairs)}")
+    if (pairs < 0).any() or (pairs >= len(frames)).any():
+        raise Rav1eHipError(f"{who}: a pair index is out of range")
+    n_planes = len(frames[0])
+    if n_planes not in (1, 3) or any(len(f) != n_planes for f in frames):
+        raise Rav1eHipError(f"{who}: every frame is 1 plane (luma) or 3 planes")
+    key = lambda d: (d.width, d.height, d.xdec, d.ydec)
+    first = [p.desc for p in frames[0]]
+    for f in frames:
+        for k, p in enumerate(f):
+            if p.desc.hbd != first[0].hbd:
+                raise Rav1eHipError(f"{who}: the frames mix 8-bit and high-bit-depth planes (hbd)")
+            if key(p.desc) != key(first[k]):
+                raise Rav1eHipError(f"{who}: the frames differ in size or decimation")
+    w, h = first[0].width, first[0].height
+    if w < 1 or h < 1 or (first[0].xdec, first[0].ydec) != (0, 0):
+        raise Rav1eHipError(f"{who}: plane 0 is the luma plane")
+    for d in first[1:]:
+        if (d.xdec, d.ydec) not in ((0, 0), (1, 0), (1, 1)) or key(d) != key(first[1]):
+            raise Rav1eHipError(f"{who}: chroma must be 4:4:4, 4:2:2 or 4:2:0")
+        if (d.width, d.height) != ((w + d.xdec) >> d.xdec, (h + d.ydec) >> d.ydec):
+            raise Rav1eHipError(f"{who}: a chroma plane's size is not the luma size rounded up "
+                                "by its decimation")
+    return n_planes, np.ascontiguousarray(pairs, dtype=np.int32)
+
+
+def frame_deltas(frames, pairs) -> np.ndarray:
+    """The sums has_scenecut (src/scenechange/mod.rs:167-207) forms over
+    Frame::iter() (PixelIter, src/frame/mod.rs:126-172), before its division:
+    frames a list of 1- or 3-tuples of DevicePlane, pairs (n, 2) indices into
+    it; returns u64 (n_pairs, n_planes).  One launch reads every frame once."""
+    n_planes, pairs = _delta_geometry(frames, pairs)
+    descs = (RvPlane * (len(frames) * n_planes))(*(p.desc for f in frames for p in f))
+    out = DeviceBuffer(8 * len(pairs) * n_planes)
+    _check(lib().rv_frame_delta_batch(descs, len(frames), n_planes, pairs.ctypes.data, len(pairs),
+                                      out.ptr, None), "rv_frame_delta_batch")
+    _sync()
+    return out.download(np.uint64, len(pairs) * n_planes).reshape(len(pairs), n_planes)
+
+
+def scenecut_threshold(bit_depth: int) -> int:
+    """SceneChangeDetector::new (src/scenechange/mod.rs:33-49): BASE_THRESHOLD
+    * bit_depth / 8."""
+    return 12 * int(bit_depth) // 8
+
+
+def fast_scene_detection(speed: int) -> bool:
+    """SpeedSettings::fast_scene_detection_preset (src/api/config.rs:409-411):
+    luma only at speed 10."""
+    return int(speed) == 10
+
+
+def keyframe_lookahead_distance(low_latency: bool = False) -> int:
+    """InterConfig::keyframe_lookahead_distance (src/api/internal.rs:182-188):
+    max(1, group_input_len) + 1, group_input_len 4 with the reorder pyramid
+    and 1 without (low_latency)."""
+    return max(1, 1 if low_latency else 4) + 1
+
+
+class SceneChangeDetector:
+    """SceneChangeDetector (src/scenechange/mod.rs) over frames in HBM: a frame
+    is a tuple of DevicePlane, (Y,) or (Y, U, V); fast_mode reads Y alone.
+
+    analyze_next_frame issues at most one frame_deltas launch: it first
+    collects the distinct frame pairs exclude_scene_flashes and is_key_frame
+    will compare, takes from the memo those an earlier call summed, and sends
+    the rest in one batch.  The memo is keyed by the pair's input frame
+    numbers and forgets pairs that reach back before input_frameno - 1.  With
+    the lookahead distance d, call N compares frame N - 1 with N .. N + d - 1
+    and N .. N + d - 2 with N + d - 1; all of these but the ones that name the
+    newest frame N + d - 1 were summed by the d - 1 calls before.  So in a
+    steady stream a call launches d pairs over d + 1 frames: 5 pairs over 6
+    frames at the reference's distance of 5, where a call on its own needs 9.
+
+    launches / launch_pairs count the batches and the pairs of each."""
+
+    def __init__(self, bit_depth: int, fast_mode: bool):
+        self.threshold = scenecut_threshold(bit_depth)
+        self.fast_mode = bool(fast_mode)
+        self.excluded_frames = set()
+        self._memo = {}  # (frameno_a, frameno_b), a < b -> plane sums
+        self.launches = 0
+        self.launch_pairs = []
+
+    # -- has_scenecut (:167-207): the part after the fold
+    def scenecut_from_sums(self, sums, length: int) -> bool:
+        if self.fast_mode:
+            delta_avg = int(sums[0]) // length
+        else:
+            d = [(int(s) // length) & 0xffff for s in sums[:3]]  # as u16
+            delta_avg = ((d[0] + d[1] + d[2]) & 0xffff) // 3
+        return delta_avg >= self.threshold
+
+    def _planes(self, frame):
+        frame = tuple(frame)
+        if self.fast_mode:
+            return frame[:1]
+        if len(frame) != 3:
+            raise Rav1eHipError("SceneChangeDetector: YUV mode needs (Y, U, V) frames")
+        return frame
+
+    def _launch(self, frames, pairs):
+        self.launches += 1
+        self.launch_pairs.append(len(pairs))
+        return frame_deltas([self._planes(f) for f in frames], pairs)
+
+    @staticmethod
+    def _len(frame):
+        d = frame[0].desc
+        return d.width * d.height
+
+    def has_scenecut(self, f1, f2) -> bool:
+        """has_scenecut of two frames outside a stream: one launch, no memo."""
+        sums = self._launch([f1, f2], [(1, 0)])[0]
+        return self.scenecut_from_sums(sums, self._len(f2))
+
+    def _fetch(self, frame_set, frameno0, wanted):
+        """Sum the pairs of `wanted` (indices into frame_set, a < b) that the
+        memo lacks, in one launch over the frames they name."""
+        missing = [p for p in dict.fromkeys(wanted)
+                   if (frameno0 + p[0], frameno0 + p[1]) not in self._memo]
+        if not missing:
+            return
+        used = sorted({i for p in missing for i in p})
+        at = {i: k for k, i in enumerate(used)}
+        sums = self._launch([frame_set[i] for i in used], [(at[a], at[b]) for a, b in missing])
+        for (a, b), s in zip(missing, sums):
+            self._memo[(frameno0 + a, frameno0 + b)] = tuple(int(v) for v in s)
+
+    def analyze_next_frame(self, previous_frame, frame_set, input_frameno, min_key_frame_interval,
+                           max_key_frame_interval, no_scene_detection, lookahead_distance,
+                           keyframes, keyframes_forced):
+        """analyze_next_frame (:58-87): frame_set[0] is frame input_frameno;
+        keyframes (a set) is updated in place."""
+        if previous_frame is None:
+            keyframes.add(0)  # The first frame is always a keyframe.
+            return
+        frame_set = [previous_frame] + list(frame_set)
+        first = input_frameno - 1  # the frame number of frame_set[0]
+        for k in [k for k in self._memo if k[0] < first]:
+            del self._memo[k]
+
+        # every comparison the two functions below can make, first
+        distance = min(lookahead_distance, len(frame_set) - 1)
+        wanted = []
+        if distance > 1:
+            wanted += [(0, j) for j in range(1, distance + 1)]
+        wanted += [(i, distance) for i in range(1, distance)]
+        if (0, 1) not in wanted and self._reaches_has_scenecut(
+                input_frameno, min_key_frame_interval, max_key_frame_interval, no_scene_detection,
+                keyframes, keyframes_forced):
+            wanted.append((0, 1))
+        self._fetch(frame_set, first, wanted)
+        length = self._len(frame_set[1])
+        cut = lambda a, b: self.scenecut_from_sums(self._memo[(first + a, first + b)], length)
+
+        self._exclude_scene_flashes(cut, len(frame_set), input_frameno, lookahead_distance)
+        if self._is_key_frame(cut, input_frameno, min_key_frame_interval, max_key_frame_interval,
+                              no_scene_detection, keyframes, keyframes_forced):
+            keyframes.add(input_frameno)
+
+    def _reaches_has_scenecut(self, frameno, min_kf, max_kf, no_scene_detection, keyframes,
+                              keyframes_forced):
+        """Whether is_key_frame gets past its early returns, given that this
+        call excludes nothing (a frame_set too short for exclude_scene_flashes
+        to compare anything)."""
+        if frameno in keyframes_forced:
+            return False
+        distance = frameno - max(keyframes)
+        return not (distance < min_kf or distance >= max_kf or no_scene_detection or
+                    frameno in self.excluded_frames)
+
+    def _is_key_frame(self, cut, current_frameno, min_kf, max_kf, no_scene_detection, keyframes,
+                      keyframes_forced):
+        """is_key_frame (:90-121)"""
+        if current_frameno in keyframes_forced:
+            return True
+        # Find the distance to the previous keyframe.
+        previous_keyframe = max(keyframes)
+        distance = current_frameno - previous_keyframe
+        # Handle minimum and maximum key frame intervals.
+        if distance < min_kf:
+            return False
+        if distance >= max_kf:
+            return True
+        # Skip smart scene detection if it's disabled
+        if no_scene_detection:
+            return False
+        if current_frameno in self.excluded_frames:
+            return False
+        return cut(0, 1)
+
+    def _exclude_scene_flashes(self, cut, n_frames, frameno, keyframe_lookahead_distance):
+        """exclude_scene_flashes (:125-164)"""
+        lookahead_distance = min(keyframe_lookahead_distance, n_frames - 1)
+        # Where A and B are scenes: AAAAAABBBAAAAAA
+        # If BBB is shorter than lookahead_distance, it is detected as a flash
+        # and not considered a scenecut.
+        if lookahead_distance > 1:
+            for j in range(1, lookahead_distance + 1):
+                if not cut(0, j):
+                    # Any frame in between `0` and `j` cannot be a real scenecut.
+                    for i in range(0, j + 1):
+                        self.excluded_frames.add(frameno + i - 1)
+        # Where A-F are scenes: AAAAABBCCDDEEFFFFFF
+        # If each of BB ... EE are shorter than `lookahead_distance`, they are
+        # detected as flashes and not considered scenecuts.
+        # Instead, the first F frame becomes a scenecut.
+        for i in range(1, lookahead_distance + 1):
+            if i < lookahead_distance and cut(i, lookahead_distance):
+                # If the current frame is the frame before a scenecut, it cannot
+                # also be the frame of a scenecut.
+                self.excluded_frames.add(frameno + i - 1)
+
+
+class KeyframeDetector:
+    """The streaming driver of the detector: ContextInner::send_frame and
+    compute_lookahead_data's first loop (src/api/internal.rs:280-330, 767-810)
+    under Context::send_frame / flush (src/api/mod.rs:304-321, 490-492).
+
+    Frame N is analysed once the last key of the frame queue is at least N +
+    distance + 1, or after flush(), which appends a None entry and sets the
+    limit to the frame count; the frame_set handed to the detector is every
+    frame from N to the end of the queue at that moment.  Only the distance +
+    2 most recent frames stay referenced (alive on the device): frame N - 1,
+    the oldest one a later analysis reads, up to the newest.  `keyframes` is
+    the set of input frame numbers chosen so far."""
+
+    def __init__(self, bit_depth: int, fast_mode: bool, min_key_frame_interval: int = 12,
+                 max_key_frame_interval: int = 240, low_latency: bool = False,
+                 no_scene_detection: bool = False):
+        self.detector = SceneChangeDetector(bit_depth, fast_mode)
+        self.min_key_frame_interval = int(min_key_frame_interval)
+        self.max_key_frame_interval = int(max_key_frame_interval)
+        self.no_scene_detection = bool(no_scene_detection)
+        self.distance = keyframe_lookahead_distance(low_latency)
+        self.frame_count = 0
+        self.limit = None
+        self.is_flushing = False
+        self.frame_q = {}  # input_frameno -> frame, or None for the end marker
+        self.last_key = None  # frame_q.keys().last(): survives the dropping of old entries
+        self.keyframes = set()
+        self.keyframes_forced = set()
+        self.next_lookahead_frame = 0
+
+    launches = property(lambda self: self.detector.launches)
+    launch_pairs = property(lambda self: self.detector.launch_pairs)
+    excluded_frames = property(lambda self: self.detector.excluded_frames)
+
+    def send_frame(self, frame, force_key: bool = False):
+        if frame is None:
+            if self.is_flushing:
+                return
+            self.limit = self.frame_count
+            self.is_flushing = True
+        elif self.is_flushing:
+            raise Rav1eHipError("KeyframeDetector: a frame after flush() (EnoughData)")
+        input_frameno = self.frame_count
+        if frame is not None:
+            self.frame_count += 1
+        self.frame_q[input_frameno] = frame
+        self.last_key = input_frameno
+        if force_key and frame is not None:
+            self.keyframes_forced.add(input_frameno)
+        self._compute_lookahead_data()
+
+    def flush(self):
+        self.send_frame(None)
+
+    def _needs_more_frames(self, frame_count):
+        return self.limit is None or frame_count < self.limit
+
+    def _needs_more_frame_q_lookahead(self, input_frameno):
+        lookahead_end = self.last_key if self.last_key is not None else 0
+        frames_needed = input_frameno + self.distance + 1
+        return lookahead_end < frames_needed and self._needs_more_frames(lookahead_end)
+
+    def _compute_lookahead_data(self):
+        lookahead_frames = [f for n, f in sorted(self.frame_q.items())
+                            if n >= self.next_lookahead_frame and f is not None]
+        lookahead_idx = 0
+        while not self._needs_more_frame_q_lookahead(self.next_lookahead_frame):
+            current_lookahead_frames = lookahead_frames[lookahead_idx:]
+            if not current_lookahead_frames:
+                break  # All frames have been processed
+            self.detector.analyze_next_frame(
+                None if self.next_lookahead_frame == 0
+                else self.frame_q.get(self.next_lookahead_frame - 1),
+                current_lookahead_frames, self.next_lookahead_frame, self.min_key_frame_interval,
+                self.max_key_frame_interval, self.no_scene_detection, self.distance,
+                self.keyframes, self.keyframes_forced)
+            self.next_lookahead_frame += 1
+            lookahead_idx += 1
+        for n in [n for n in self.frame_q if n < self.next_lookahead_frame - 1]:
+            del self.frame_q[n]  # nothing reads them again
 
 
 def deblock_plane(plane: DevicePlane, pli, width, height, lg: np.ndarray, skip: np.ndarray,

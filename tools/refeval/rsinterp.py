@@ -257,6 +257,9 @@ class Parser:
             if self.at("<"):
                 self.next()
                 gens = self.parse_generic_args()
+            elif self.at("<<"):  # Option<<Self as Iterator>::Item>: the first `<` opens the args
+                self.peek().text = "<"
+                gens = self.parse_generic_args()
             if self.at("::") and self.peek(1).kind == "id":
                 self.next()
                 segs.append(self.ident())
