@@ -527,6 +527,35 @@ int rv_ec_tokenize(const rv_ec_job *d_jobs, int n, int xdec, int ydec, int n_til
  * then done(): returns the byte count, the bytes go to out if they fit in
  * cap.  cdf: the tile's CDFs (rv_ec_cdf_total() u16, updated in place). */
 long rv_ec_code_tokens(const uint32_t *tokens, size_t n, uint16_t *cdf, uint8_t *out, size_t cap);
+/* rv_ec_count_tokens (host): the same tokens through WriterBase<
+ * WriterCounter> (src/ec.rs:187-205), the writer encode_tx_block prices
+ * cost_coeffs with under the RealRate RDO types (src/encoder.rs:1172-1190).
+ * Returns tell_frac() after minus tell_frac() before (:366-388, 765-780), in
+ * 1/8 bit (OD_BITRES = 3), or RV_EINVAL for a bad token / state.  cdf adapts
+ * in place.  state (may be NULL: a fresh writer, rng 0x8000, cnt -9, no
+ * bytes) holds {rng, (uint16_t)cnt, bytes} and is updated, so a stream may
+ * be counted in pieces. */
+long rv_ec_count_tokens(const uint32_t *tokens, size_t n, uint16_t *cdf, uint32_t *state);
+/* rv_ec_rate_batch: that count for every candidate of a round, one
+ * wavefront per candidate.  Group g is the consecutive jobs
+ * [d_group_first[g], d_group_first[g + 1]) of an rv_ec_tokenize result
+ * (d_group_first: n_groups + 1 ascending job indices), its tokens
+ * d_tokens[d_offsets[first[g]] .. d_offsets[first[g + 1]]).  They go through
+ * one counter with a private copy of snapshot d_group_cdf[g] (NULL: snapshot
+ * 0) of d_cdfs (n_cdfs snapshots of rv_ec_cdf_total() u16 each, read only);
+ * the copy adapts from block to block inside the group, as the reference's
+ * ContextWriter does between a candidate's luma and chroma blocks, and is
+ * dropped afterwards (cw.rollback).  d_init (may be NULL: fresh writers):
+ * per group rng | (uint16_t)cnt << 16, the writer state after the symbols
+ * that precede the coefficients.  d_rate[g]: the tell_frac() difference
+ * modulo 2^32; 0 for a group without tokens.  A group with a bad token (the
+ * test of rv_ec_code_tokens) or a snapshot index outside [0, n_cdfs) stops
+ * there, rates 0xFFFFFFFF and adds 1 to d_status[0] (cleared here); neither
+ * is used as an index.  d_group_first and d_offsets are trusted. */
+int rv_ec_rate_batch(const uint32_t *d_tokens, const uint32_t *d_offsets,
+                     const int32_t *d_group_first, int n_groups, const uint16_t *d_cdfs,
+                     int n_cdfs, const int32_t *d_group_cdf, const uint32_t *d_init,
+                     uint32_t *d_rate, uint32_t *d_status, void *stream);
 /* CDFContext::new(quantizer) coefficient CDFs for q context qctx 0..3
  * (src/context.rs:793-850: base_q_idx <= 20, <= 60, <= 120, else 3) and
  * CDFContext::reset_counts (:851-) over them. */

@@ -334,6 +334,8 @@ def _declare(L):
         "rv_ec_tokenize": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_uint32, vp,
                                  vp]),
         "rv_ec_code_tokens": (C.c_long, [vp, C.c_size_t, vp, vp, C.c_size_t]),
+        "rv_ec_count_tokens": (C.c_long, [vp, C.c_size_t, vp, vp]),
+        "rv_ec_rate_batch": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
         "rv_ec_cdf_total": (i32, []),
         "rv_ec_default_cdf": (i32, [i32, vp]),
         "rv_ec_reset_counts": (None, [vp]),
@@ -1301,6 +1303,9 @@ EC_JOB = np.dtype({"names": ["kind", "plane", "bx", "by", "tx_size", "tx_type", 
                    "offsets": [4 * i for i in range(10)] + [40], "itemsize": 48})
 
 
+EC_BITRES = 3  # OD_BITRES (src/ec.rs): rates are in 1/8 bit
+
+
 def ec_default_cdf(qctx):
     """CDFContext::new's coefficient CDFs for q context qctx (flat u16)."""
     out = np.zeros(lib().rv_ec_cdf_total(), np.uint16)
@@ -1326,6 +1331,69 @@ def ec_code_tokens(tokens, cdf):
     return out[:n]
 
 
+def ec_count_tokens(tokens, cdf, state=None):
+    """tokens through the host bit counter (WriterBase<WriterCounter>): the
+    tell_frac() difference in 1 / 2**EC_BITRES bit; cdf adapts in place.
+    state: (rng, cnt, bytes) of the writer before (None: a fresh writer).
+    Returns (rate, state after)."""
+    tokens = np.ascontiguousarray(tokens, np.uint32)
+    rng, cnt, nbytes = (0x8000, -9, 0) if state is None else (int(v) for v in state)
+    st = np.array([rng, cnt & 0xFFFF, nbytes], np.uint32)
+    c2 = np.array(cdf, np.uint16)
+    rate = lib().rv_ec_count_tokens(tokens.ctypes.data, tokens.size, c2.ctypes.data,
+                                    st.ctypes.data)
+    if rate < 0:
+        _check(int(rate), "rv_ec_count_tokens")
+    cdf[:] = c2
+    cnt = int(st[1])
+    return int(rate), (int(st[0]), cnt - 0x10000 if cnt & 0x8000 else cnt, int(st[2]))
+
+
+class _EcTokens:
+    """rv_ec_tokenize of a coding-order job list: the device buffers and the
+    tile starts."""
+
+    def __init__(self, jobs, coeffs, xdec, ydec, what):
+        jobs = np.asarray(jobs, np.int64)
+        n = len(jobs)
+        self.n = n
+        self.co = DeviceBuffer.from_array(np.ascontiguousarray(coeffs, np.int32))
+        ej = np.zeros(n, EC_JOB)
+        for k, f in enumerate(["kind", "plane", "bx", "by", "tx_size", "tx_type", "is_inter",
+                               "bw_lg", "bh_lg"]):
+            ej[f] = jobs[:, k]
+        starts = np.nonzero(jobs[:, 0] == 3)[0]
+        if len(starts) == 0 or starts[0] != 0:
+            starts = np.concatenate([[0], starts])
+        tile = np.cumsum(jobs[:, 0] == 3) - 1
+        ej["tile"] = np.maximum(tile, 0)
+        ej["coeffs"] = self.co.ptr + 4 * jobs[:, 9].astype(np.uint64)
+        self.starts, self.ntiles = starts, len(starts)
+        ext = np.where(jobs[:, 0] == 0, 1 << jobs[:, 4], np.where(jobs[:, 0] == 1, 1 << np.maximum(jobs[:, 7] - 2, 0), 0))
+        mw = int(max(1, (jobs[:, 2] + ext).max()))
+        mh = int(max(1, (jobs[:, 3] + ext).max()))
+        dj = DeviceBuffer.from_array(ej)
+        dmap = DeviceBuffer(self.ntiles * 3 * mw * mh)
+        scr = DeviceBuffer(lib().rv_ec_scratch_bytes(n))
+        self.doff = DeviceBuffer(4 * (n + 1))
+        cap = int(64 * n + 8 * int(np.asarray(coeffs).size) + 1024)
+        self.dtok = DeviceBuffer(4 * cap)
+        dst = DeviceBuffer(8)
+        _check(lib().rv_ec_tokenize(dj.ptr, n, xdec, ydec, self.ntiles, mw, mh, dmap.ptr, scr.ptr,
+                                    self.doff.ptr, self.dtok.ptr, cap, dst.ptr, None),
+               "rv_ec_tokenize")
+        _sync(None)
+        self.status = dst.download(np.uint32)
+        if self.status[1]:
+            raise Rav1eHipError(what + ": token buffer overflow")
+
+    def offsets(self):
+        return self.doff.download(np.uint32)[:self.n + 1]
+
+    def tokens(self):
+        return self.dtok.download(np.uint32)[:int(self.status[0])]
+
+
 def code_coefficients(jobs, coeffs, cdf_init, xdec, ydec):
     """A coding-order job sequence (rows kind, plane, bx, by, tx_size, tx_type,
     is_inter, bw_lg, bh_lg, coeff_off; kind 3 starts a tile) through the
@@ -1333,38 +1401,10 @@ def code_coefficients(jobs, coeffs, cdf_init, xdec, ydec):
     transform block, reset_skip_context / reset_left_contexts between them.
     Returns (bytes of all tiles, bytes per tile, the last tile's final CDFs,
     tokens)."""
-    jobs = np.asarray(jobs, np.int64)
-    n = len(jobs)
-    co = DeviceBuffer.from_array(np.ascontiguousarray(coeffs, np.int32))
-    ej = np.zeros(n, EC_JOB)
-    for k, f in enumerate(["kind", "plane", "bx", "by", "tx_size", "tx_type", "is_inter",
-                           "bw_lg", "bh_lg"]):
-        ej[f] = jobs[:, k]
-    starts = np.nonzero(jobs[:, 0] == 3)[0]
-    if len(starts) == 0 or starts[0] != 0:
-        starts = np.concatenate([[0], starts])
-    tile = np.cumsum(jobs[:, 0] == 3) - 1
-    ej["tile"] = np.maximum(tile, 0)
-    ej["coeffs"] = co.ptr + 4 * jobs[:, 9].astype(np.uint64)
-    ntiles = len(starts)
-    ext = np.where(jobs[:, 0] == 0, 1 << jobs[:, 4], np.where(jobs[:, 0] == 1, 1 << np.maximum(jobs[:, 7] - 2, 0), 0))
-    mw = int(max(1, (jobs[:, 2] + ext).max()))
-    mh = int(max(1, (jobs[:, 3] + ext).max()))
-    dj = DeviceBuffer.from_array(ej)
-    dmap = DeviceBuffer(ntiles * 3 * mw * mh)
-    scr = DeviceBuffer(lib().rv_ec_scratch_bytes(n))
-    doff = DeviceBuffer(4 * (n + 1))
-    cap = int(64 * n + 8 * int(np.asarray(coeffs).size) + 1024)
-    dtok = DeviceBuffer(4 * cap)
-    dst = DeviceBuffer(8)
-    _check(lib().rv_ec_tokenize(dj.ptr, n, xdec, ydec, ntiles, mw, mh, dmap.ptr, scr.ptr, doff.ptr,
-                                dtok.ptr, cap, dst.ptr, None), "rv_ec_tokenize")
-    _sync(None)
-    status = dst.download(np.uint32)
-    if status[1]:
-        raise Rav1eHipError("code_coefficients: token buffer overflow")
-    off = doff.download(np.uint32)[:n + 1]
-    tok = dtok.download(np.uint32)[:int(status[0])]
+    tk = _EcTokens(jobs, coeffs, xdec, ydec, "code_coefficients")
+    n, ntiles, starts = tk.n, tk.ntiles, tk.starts
+    off = tk.offsets()
+    tok = tk.tokens()
     out, tb, cdf = [], [], None
     for t in range(ntiles):
         a = int(off[starts[t]])
@@ -1374,6 +1414,54 @@ def code_coefficients(jobs, coeffs, cdf_init, xdec, ydec):
         out.append(by)
         tb.append(len(by))
     return np.concatenate(out), np.array(tb, np.int32), cdf, tok
+
+
+def ec_rate_batch(tokens, offsets, group_first, cdfs, group_cdf=None, init=None):
+    """rv_ec_rate_batch over device or host arrays: tokens / offsets are
+    DeviceBuffers or arrays (uploaded), the rest host arrays.  cdfs: (n_cdfs,
+    rv_ec_cdf_total()) u16.  Returns (rates u32 per group, d_status[0], the
+    snapshots as the device holds them after the call)."""
+    def dev(x, dt):
+        return x if isinstance(x, DeviceBuffer) else DeviceBuffer.from_array(np.asarray(x, dt))
+    group_first = np.ascontiguousarray(group_first, np.int32)
+    ng = len(group_first) - 1
+    cdfs = np.ascontiguousarray(cdfs, np.uint16).reshape(-1, lib().rv_ec_cdf_total())
+    dtok, doff = dev(tokens, np.uint32), dev(offsets, np.uint32)
+    dgf, dcdf = DeviceBuffer.from_array(group_first), DeviceBuffer.from_array(cdfs)
+    dgc = None if group_cdf is None else DeviceBuffer.from_array(
+        np.ascontiguousarray(group_cdf, np.int32))
+    dini = None if init is None else DeviceBuffer.from_array(
+        np.ascontiguousarray(init, np.uint32))
+    if (dgc is not None and dgc.nbytes != 4 * ng) or (dini is not None and dini.nbytes != 4 * ng):
+        raise Rav1eHipError("ec_rate_batch: group_cdf / init need one entry per group")
+    drate, dst = DeviceBuffer(4 * ng), DeviceBuffer(4)
+    _check(lib().rv_ec_rate_batch(dtok.ptr, doff.ptr, dgf.ptr, ng, dcdf.ptr, len(cdfs),
+                                  dgc.ptr if dgc else None, dini.ptr if dini else None,
+                                  drate.ptr, dst.ptr, None), "rv_ec_rate_batch")
+    _sync(None)
+    return (drate.download(np.uint32, ng), int(dst.download(np.uint32)[0]),
+            dcdf.download(np.uint16).reshape(cdfs.shape))
+
+
+def coefficient_rates(jobs, coeffs, group_first, cdfs, xdec, ydec, group_cdf=None, init=None):
+    """The real coefficient rate of every candidate (cost_coeffs of
+    encode_tx_block under the RealRate RDO types, src/encoder.rs:1172-1190):
+    the job list through the device tokenizer (as code_coefficients), then
+    each group -- the jobs [group_first[g], group_first[g + 1]) -- through a
+    counting writer on the device, with a private copy of snapshot
+    group_cdf[g] (default 0) of cdfs that adapts inside the group and is
+    dropped after it.  init: per group rng | (cnt & 0xFFFF) << 16 (default:
+    fresh writers).  Returns (rates in 1 / 2**EC_BITRES bit, tokens,
+    offsets)."""
+    tk = _EcTokens(jobs, coeffs, xdec, ydec, "coefficient_rates")
+    group_first = np.ascontiguousarray(group_first, np.int32)
+    if len(group_first) < 1 or group_first[0] < 0 or group_first[-1] > tk.n or \
+            np.any(np.diff(group_first) < 0):
+        raise Rav1eHipError("coefficient_rates: group_first must ascend within the job list")
+    rates, bad, _ = ec_rate_batch(tk.dtok, tk.doff, group_first, cdfs, group_cdf, init)
+    if bad:
+        raise Rav1eHipError(f"coefficient_rates: {bad} groups with a bad token or snapshot index")
+    return rates, tk.tokens(), tk.offsets()
 
 
 def prep_8tap_batch(src: DevicePlane, jobs, w, h, mode_x=0, mode_y=0, bit_depth=8):

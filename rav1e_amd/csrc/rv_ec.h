@@ -37,6 +37,93 @@ struct EcFrameBufs {
   uint32_t *dstat;       // device [total, overflow]
 };
 
+// ---- the range coder's arithmetic, shared by the host encoder, the host
+// counter (rv_ec.hip) and the device counter (rv_ec_rate.hip)
+// lr_compute (src/ec.rs:339-355): the low offset and the new range
+__host__ __device__ inline void ec_lr_compute(uint32_t r, uint32_t fl, uint32_t fh, uint32_t nms,
+                                              uint32_t &l, uint32_t &rr) {
+  if (fl < 32768) {
+    const uint32_t u = (((r >> 8) * (fl >> 6)) >> 1) + 4 * nms;
+    const uint32_t v = (((r >> 8) * (fh >> 6)) >> 1) + 4 * (nms - 1);
+    l = r - u;
+    rr = (u - v) & 0xFFFF;
+  } else {
+    l = 0;
+    rr = (r - ((((r >> 8) * (fh >> 6)) >> 1) + 4 * (nms - 1))) & 0xFFFF;
+  }
+}
+// 16 - ilog(u16) of a range (16 for 0, which no valid state reaches)
+__host__ __device__ inline int ec_norm_shift(uint32_t rr) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __clz((int)rr) - 16;
+#else
+  return rr ? __builtin_clz(rr) - 16 : 16;
+#endif
+}
+// update_cdf (src/ec.rs:891-905): the adaptation rate of a CDF of nsymbs
+// symbols whose counter is `count`, and one entry's step.  A rate of 16
+// shifts a u16 entry to 0 like every larger one (only a counter that is not
+// one gives it), so the shift count stays in range.
+__host__ __device__ inline int ec_cdf_rate(int nsymbs, uint32_t count) {
+  const int rate = 3 + (nsymbs >> 1 < 2 ? nsymbs >> 1 : 2) + (int)(count >> 4);
+  return rate < 16 ? rate : 16;
+}
+__host__ __device__ inline uint16_t ec_cdf_step(uint32_t v, int rate, bool below) {
+  return below ? (uint16_t)(v + ((32768 - (int)v) >> rate)) : (uint16_t)(v - (v >> rate));
+}
+__host__ __device__ inline uint16_t ec_cdf_count(uint32_t count) {
+  return (uint16_t)(count + 1 - (count >> 5));
+}
+
+// WriterBase<WriterCounter> (src/ec.rs:187-205, 366-388, 765-780)
+struct EcCounter {
+  uint32_t rng = 0x8000;
+  int32_t cnt = -9;
+  uint32_t bytes = 0;
+  __host__ __device__ inline void store(uint32_t fl, uint32_t fh, uint32_t nms) {
+    uint32_t l, rr;
+    ec_lr_compute(rng, fl, fh, nms, l, rr);
+    const int d = ec_norm_shift(rr);
+    int c = cnt, s = c + d;
+    if (s >= 0) {
+      c += 16;
+      if (s >= 8) {
+        bytes++;
+        c -= 8;
+      }
+      bytes++;
+      s = c + d - 24;
+    }
+    rng = (rr << d) & 0xFFFF;
+    cnt = (int16_t)s;
+  }
+  __host__ __device__ inline void bit(uint32_t b) {  // bool(b, 16384)
+    store(b ? 16384u : 32768u, b ? 0u : 16384u, b ? 1u : 2u);
+  }
+  // frac_compute's fraction of the range (OD_BITRES = 3 bits)
+  __host__ __device__ inline uint32_t frac() const {
+    uint32_t r = rng, l = 0;
+    for (int i = 0; i < 3; i++) {
+      r = (r * r) >> 15;
+      const uint32_t b = r >> 16;
+      l = (l << 1) | b;
+      r >>= b;
+    }
+    return l;
+  }
+  // tell_frac() = (tell() << OD_BITRES) - frac, modulo 2^32
+  __host__ __device__ inline uint32_t tell_frac() const {
+    return ((bytes * 8 + (uint32_t)cnt + 10) << 3) - frac();
+  }
+};
+// a token's fields and the test both counters and the encoder apply to it
+__host__ __device__ inline bool ec_token_ok(uint32_t t, int total, int &off, int &len, int &s) {
+  off = (int)(t & 0x1FFF);
+  len = (int)((t >> 13) & 31);
+  s = (int)((t >> 18) & 31);
+  return !(off + len > total || len < 2 || s >= len - 1);
+}
+
 int ec_frame_tokens(const EcFrameArgs &a, const EcFrameBufs &b, hipStream_t st);
 // worst-case jobs of a group of nsb superblocks (8x8 leaves at 4:2:0 or
 // 64x64 leaves with four chroma transforms at 4:4:4)

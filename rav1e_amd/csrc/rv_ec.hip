@@ -674,6 +674,13 @@ using namespace rv;
 // ------------------------------------------------------------ host coder
 namespace {
 
+// update_cdf (src/ec.rs:891-905) of a CDF of nsymbs symbols + its counter
+inline void update_cdf(uint16_t *cdf, int nsymbs, uint32_t s) {
+  const int rate = ec_cdf_rate(nsymbs, cdf[nsymbs]);
+  cdf[nsymbs] = ec_cdf_count(cdf[nsymbs]);
+  for (int i = 0; i < nsymbs - 1; i++) cdf[i] = ec_cdf_step(cdf[i], rate, (uint32_t)i < s);
+}
+
 struct EcWriter {  // WriterBase<WriterEncoder> (src/ec.rs:100-600)
   uint32_t low = 0;
   uint16_t rng = 0x8000;
@@ -682,20 +689,11 @@ struct EcWriter {  // WriterBase<WriterEncoder> (src/ec.rs:100-600)
 
   // lr_compute + store (src/ec.rs:270-295, 339-364)
   inline void store(uint32_t fl, uint32_t fh, uint32_t nms) {
-    const uint32_t r = rng;
     uint32_t l, rr;
-    if (fl < 32768) {
-      const uint32_t u = (((r >> 8) * (fl >> 6)) >> 1) + 4 * nms;
-      const uint32_t v = (((r >> 8) * (fh >> 6)) >> 1) + 4 * (nms - 1);
-      l = r - u;
-      rr = (u - v) & 0xFFFF;
-    } else {
-      l = 0;
-      rr = (r - ((((r >> 8) * (fh >> 6)) >> 1) + 4 * (nms - 1))) & 0xFFFF;
-    }
+    ec_lr_compute(rng, fl, fh, nms, l, rr);
     uint32_t lo = l + low;
     int c = cnt;
-    const int d = __builtin_clz(rr) - 16;  // 16 - ilog(u16)
+    const int d = ec_norm_shift(rr);  // 16 - ilog(u16)
     int s = c + d;
     if (s >= 0) {
       c += 16;
@@ -719,12 +717,7 @@ struct EcWriter {  // WriterBase<WriterEncoder> (src/ec.rs:100-600)
     const int n = len - 1;
     const uint32_t fl = s > 0 ? cdf[s - 1] : 32768u;
     store(fl, cdf[s], (uint32_t)(n - (int)s));
-    const int nsymbs = n;
-    const int rate = 3 + (nsymbs >> 1 < 2 ? nsymbs >> 1 : 2) + (cdf[nsymbs] >> 4);
-    cdf[nsymbs] = (uint16_t)(cdf[nsymbs] + 1 - (cdf[nsymbs] >> 5));
-    for (int i = 0; i < nsymbs - 1; i++)
-      cdf[i] = (uint32_t)i >= s ? (uint16_t)(cdf[i] - (cdf[i] >> rate))
-                                : (uint16_t)(cdf[i] + ((32768 - cdf[i]) >> rate));
+    update_cdf(cdf, n, s);
   }
   inline void bit(uint32_t b) {  // bool(b, 16384): symbol over [16384, 0]
     store(b ? 16384u : 32768u, b ? 0u : 16384u, b ? 1u : 2u);
@@ -773,8 +766,8 @@ long rv_ec_code_tokens(const uint32_t *tok, size_t n, uint16_t *cdf, uint8_t *ou
     if (t >> 31) {
       w.bit(t & 1);
     } else {
-      const int off = (int)(t & 0x1FFF), len = (int)((t >> 13) & 31), s = (int)((t >> 18) & 31);
-      if (off + len > RV_EC_TOTAL || len < 2 || s >= len - 1)
+      int off, len, s;
+      if (!ec_token_ok(t, RV_EC_TOTAL, off, len, s))
         return rv_set_error(RV_EINVAL, "rv_ec_code_tokens: bad token");
       w.symbol_update((uint32_t)s, cdf + off, len);
     }
@@ -782,6 +775,40 @@ long rv_ec_code_tokens(const uint32_t *tok, size_t n, uint16_t *cdf, uint8_t *ou
   const size_t nb = w.finish();
   if (out && nb <= cap) w.bytes(out);
   return (long)nb;
+}
+
+long rv_ec_count_tokens(const uint32_t *tok, size_t n, uint16_t *cdf, uint32_t *state) {
+  if (!tok && n) return rv_set_error(RV_EINVAL, "rv_ec_count_tokens: null tokens");
+  if (!cdf) return rv_set_error(RV_EINVAL, "rv_ec_count_tokens: null cdf");
+  EcCounter w;
+  if (state) {
+    if (state[0] < 0x8000 || state[0] > 0xFFFF || state[1] > 0xFFFF)
+      return rv_set_error(RV_EINVAL, "rv_ec_count_tokens: bad state");
+    w.rng = state[0];
+    w.cnt = (int16_t)state[1];
+  }
+  // the byte count enters the rate only through its growth: w counts from 0
+  const long before = 8 * (long)w.cnt - (long)w.frac();
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t t = tok[i];
+    if (t >> 31) {
+      w.bit(t & 1);
+    } else {
+      int off, len, s;
+      if (!ec_token_ok(t, RV_EC_TOTAL, off, len, s))
+        return rv_set_error(RV_EINVAL, "rv_ec_count_tokens: bad token");
+      uint16_t *c = cdf + off;
+      w.store(s > 0 ? c[s - 1] : 32768u, c[s], (uint32_t)(len - 1 - s));
+      update_cdf(c, len - 1, (uint32_t)s);
+    }
+  }
+  const long rate = 64 * (long)w.bytes + 8 * (long)w.cnt - (long)w.frac() - before;
+  if (state) {
+    state[0] = w.rng;
+    state[1] = (uint16_t)w.cnt;
+    state[2] += w.bytes;
+  }
+  return rate;
 }
 
 int rv_ec_default_cdf(int qctx, uint16_t *out) {
