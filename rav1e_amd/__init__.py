@@ -211,6 +211,13 @@ class FilterMode(enum.IntEnum):
 _lib = None
 
 
+class RvEcModeParams(C.Structure):
+    """rv_ec_mode_params (include/rav1e_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("frame_type", "reference_mode", "force_integer_mv",
+                                         "allow_high_precision_mv", "seg_enabled",
+                                         "last_active_segid")]
+
+
 def _declare(L):
     vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
     P = C.POINTER(RvPlane)
@@ -339,6 +346,14 @@ def _declare(L):
         "rv_ec_cdf_total": (i32, []),
         "rv_ec_default_cdf": (i32, [i32, vp]),
         "rv_ec_reset_counts": (None, [vp]),
+        "rv_ec_mode_scratch_bytes": (C.c_size_t, [i32]),
+        "rv_ec_mode_tokenize": (i32, [vp, i32, RvEcModeParams, i32, vp, i32, i32, vp, vp, vp, vp,
+                                      C.c_uint32, vp, vp]),
+        "rv_ec_code_stream": (C.c_long, [vp, C.c_size_t, vp, vp, C.c_size_t]),
+        "rv_ec_count_stream": (C.c_long, [vp, C.c_size_t, vp, vp]),
+        "rv_ec_cdf_total_all": (i32, []),
+        "rv_ec_default_cdf_all": (i32, [i32, vp]),
+        "rv_ec_reset_counts_all": (None, [vp]),
         "rv_sad_fn": (vp, [i32, i32, i32]),
         "rv_satd_fn": (vp, [i32, i32, i32]),
         "rv_put_fn_get": (vp, [i32, i32, i32]),
@@ -571,7 +586,7 @@ def put_8tap_batch(dst: DevicePlane, src: DevicePlane, jobs, w, h, mode_x=0, mod
 
 
 class PredictionMode(enum.IntEnum):
-    """src/predict.rs:135-166 (the intra modes)."""
+    """src/predict.rs:135-166."""
     DC_PRED = 0
     V_PRED = 1
     H_PRED = 2
@@ -586,6 +601,20 @@ class PredictionMode(enum.IntEnum):
     SMOOTH_H_PRED = 11
     PAETH_PRED = 12
     UV_CFL_PRED = 13
+    NEARESTMV = 14
+    NEAR0MV = 15
+    NEAR1MV = 16
+    NEAR2MV = 17
+    GLOBALMV = 18
+    NEWMV = 19
+    NEAREST_NEARESTMV = 20
+    NEAR_NEARMV = 21
+    NEAREST_NEWMV = 22
+    NEW_NEARESTMV = 23
+    NEAR_NEWMV = 24
+    NEW_NEARMV = 25
+    GLOBAL_GLOBALMV = 26
+    NEW_NEWMV = 27
 
 
 # RAV1E_INTRA_MODES (src/predict.rs:32-46): the screening order
@@ -1414,6 +1443,233 @@ def code_coefficients(jobs, coeffs, cdf_init, xdec, ydec):
         out.append(by)
         tb.append(len(by))
     return np.concatenate(out), np.array(tb, np.int32), cdf, tok
+
+
+# ---- block mode info (rv_ec_mode.hip) ---------------------------------------
+_EC_MODE_FIELDS = ["kind", "tile", "bx", "by", "bsize", "partition", "skip", "seg_idx",
+                   "luma_mode", "chroma_mode", "ref0", "ref1", "mv0_row", "mv0_col", "mv1_row",
+                   "mv1_col", "ref_mv0_row", "ref_mv0_col", "ref_mv1_row", "ref_mv1_col",
+                   "mode_context", "num_mv_found", "weight0", "weight1", "weight2", "weight3",
+                   "cfl_joint_sign", "cfl_scale_u", "cfl_scale_v", "reserved0", "reserved1",
+                   "reserved2"]
+# rv_ec_mode_job: 32 int32 (ref[2], mv[4], ref_mv[4], weight[4], cfl_scale[2] flattened)
+EC_MODE_JOB = np.dtype({"names": _EC_MODE_FIELDS, "formats": [np.int32] * 32,
+                        "offsets": [4 * i for i in range(32)], "itemsize": 128})
+FRAME_KEY, FRAME_INTER = 0, 1
+REF_CAT_LEVEL = 640
+
+
+class EcModeParams:
+    """The frame parameters of rv_ec_mode_tokenize and every tile's (cols,
+    rows) in luma 4x4 units.  reference_mode: 0 ReferenceMode::SINGLE."""
+
+    def __init__(self, frame_type=FRAME_INTER, reference_mode=0, force_integer_mv=0,
+                 allow_high_precision_mv=0, seg_enabled=0, last_active_segid=0,
+                 tile_dims=((16, 16),)):
+        self.frame_type, self.reference_mode = int(frame_type), int(reference_mode)
+        self.force_integer_mv = int(force_integer_mv)
+        self.allow_high_precision_mv = int(allow_high_precision_mv)
+        self.seg_enabled, self.last_active_segid = int(seg_enabled), int(last_active_segid)
+        self.tile_dims = np.ascontiguousarray(tile_dims, np.int32).reshape(-1, 2)
+
+    def c_struct(self):
+        return RvEcModeParams(self.frame_type, self.reference_mode, self.force_integer_mv,
+                              self.allow_high_precision_mv, self.seg_enabled,
+                              self.last_active_segid)
+
+
+def ec_mode_jobs(rows):
+    """An (n, <= 32) integer array in EC_MODE_JOB's field order as EC_MODE_JOB."""
+    rows = np.asarray(rows, np.int64)
+    rows = rows.reshape(-1, rows.shape[-1] if rows.ndim > 1 else 32)
+    out = np.zeros(len(rows), EC_MODE_JOB)
+    for k, f in enumerate(_EC_MODE_FIELDS[:rows.shape[1]]):
+        out[f] = rows[:, k]
+    return out
+
+
+def _mode_has_near(m):
+    P = PredictionMode
+    return P.NEAR0MV <= m <= P.NEAR2MV or m in (P.NEAR_NEARMV, P.NEAR_NEWMV, P.NEW_NEARMV)
+
+
+def check_mode_jobs(jobs, stack_mvs=None):
+    """The assert!s of encode_block_post_cdef (src/encoder.rs:1537-1617) and
+    write_ref_frames on a job list: NEW_NEWMV needs two stack entries, a NEAR
+    mode its stack entry, NEARESTMV / a NEAR mode the stack's MV (NEARESTMV
+    against ref_mv, the stack's entry 0; the NEAR modes against stack_mvs
+    (n, 4, 2) row / col when given), a compound block a width of 8."""
+    P = PredictionMode
+    for i, j in enumerate(np.asarray(jobs)):
+        m = int(j["luma_mode"])
+        if int(j["kind"]) != 0 or m < P.NEARESTMV:
+            continue
+        nf = int(j["num_mv_found"])
+        mv0 = (int(j["mv0_row"]), int(j["mv0_col"]))
+        if m >= P.NEAREST_NEARESTMV and int(j["bsize"]) < BlockSize.BLOCK_8X8:
+            raise Rav1eHipError(f"job {i}: a compound block below 8x8")
+        if m == P.NEW_NEWMV and nf < 2:
+            raise Rav1eHipError(f"job {i}: NEW_NEWMV with {nf} MV stack entries")
+        if _mode_has_near(m):
+            idx = m - P.NEAR0MV + 1 if m <= P.NEAR2MV else 1
+            if m != P.NEAR0MV and nf <= idx:
+                raise Rav1eHipError(f"job {i}: a NEAR mode without its MV stack entry")
+            if stack_mvs is not None:
+                want = tuple(int(v) for v in stack_mvs[i][idx]) if nf > 1 else (0, 0)
+                if mv0 != want:
+                    raise Rav1eHipError(f"job {i}: a NEAR mode whose MV is not the stack's")
+        elif m == P.NEARESTMV:
+            want = (int(j["ref_mv0_row"]), int(j["ref_mv0_col"])) if nf else (0, 0)
+            if mv0 != want:
+                raise Rav1eHipError(f"job {i}: NEARESTMV whose MV is not the stack's")
+
+
+def resolve_skip_segments(jobs, params):
+    """write_segmentation stores its prediction into a skip block
+    (src/context.rs:3536-3544, get_segment_pred :3465-3505) and later
+    neighbours read it: a serial walk in coding order that fills the skip
+    blocks' seg_idx with what the reference stores.  The identity with
+    segmentation off or every block in segment 0.  Returns a copy."""
+    jobs = np.array(jobs, EC_MODE_JOB)
+    if not params.seg_enabled or not jobs["seg_idx"].any():
+        return jobs
+    maps = {}
+    for j in jobs:
+        if j["kind"] != 0 or j["bsize"] not in (3, 6, 9, 12):
+            continue
+        t = int(j["tile"])
+        if not 0 <= t < len(params.tile_dims):
+            continue
+        cols, rows = (int(v) for v in params.tile_dims[t])
+        bx, by = int(j["bx"]), int(j["by"])
+        if not (0 <= bx < cols and 0 <= by < rows):
+            continue
+        m = maps.setdefault(t, np.zeros(((rows + 1) // 2 + 8, (cols + 1) // 2 + 8), np.int32))
+        x, y, n8 = bx >> 1, by >> 1, 1 << (int(j["bsize"]) // 3 - 1)
+        if j["skip"]:
+            ul = m[y - 1, x - 1] if bx > 0 and by > 0 else -1
+            u = m[y - 1, x] if by > 0 else -1
+            l = m[y, x - 1] if bx > 0 else -1
+            if u == -1:
+                j["seg_idx"] = 0 if l == -1 else l
+            elif l == -1:
+                j["seg_idx"] = u
+            else:
+                j["seg_idx"] = u if ul == u else l
+        m[y:y + n8, x:x + n8] = j["seg_idx"]
+    return jobs
+
+
+def ec_default_cdf_all(qctx):
+    """CDFContext::new's CDFs in the combined layout (coefficients, then mode info)."""
+    out = np.zeros(lib().rv_ec_cdf_total_all(), np.uint16)
+    _check(lib().rv_ec_default_cdf_all(qctx, out.ctypes.data), "rv_ec_default_cdf_all")
+    return out
+
+
+def ec_code_stream(tokens, cdf_all):
+    """One tile's mixed tokens through the host range coder; cdf_all adapts in place."""
+    tokens = np.ascontiguousarray(tokens, np.uint32)
+    out = np.zeros(tokens.size // 2 + 4096, np.uint8)
+    c2 = np.array(cdf_all, np.uint16)
+    n = lib().rv_ec_code_stream(tokens.ctypes.data, tokens.size, c2.ctypes.data, out.ctypes.data,
+                                out.size)
+    if n < 0:
+        _check(int(n), "rv_ec_code_stream")
+    if n > out.size:
+        out = np.zeros(n, np.uint8)
+        c2 = np.array(cdf_all, np.uint16)
+        lib().rv_ec_code_stream(tokens.ctypes.data, tokens.size, c2.ctypes.data, out.ctypes.data,
+                                out.size)
+    cdf_all[:] = c2
+    return out[:n]
+
+
+def ec_count_stream(tokens, cdf_all, state=None):
+    """ec_count_tokens over the combined table and mixed tokens."""
+    tokens = np.ascontiguousarray(tokens, np.uint32)
+    rng, cnt, nbytes = (0x8000, -9, 0) if state is None else (int(v) for v in state)
+    st = np.array([rng, cnt & 0xFFFF, nbytes], np.uint32)
+    c2 = np.array(cdf_all, np.uint16)
+    rate = lib().rv_ec_count_stream(tokens.ctypes.data, tokens.size, c2.ctypes.data,
+                                    st.ctypes.data)
+    if rate < 0:
+        _check(int(rate), "rv_ec_count_stream")
+    cdf_all[:] = c2
+    cnt = int(st[1])
+    return int(rate), (int(st[0]), cnt - 0x10000 if cnt & 0x8000 else cnt, int(st[2]))
+
+
+def ec_tokenize_modes(jobs, params, stack_mvs=None, check=True):
+    """rv_ec_mode_tokenize of a coding-order EC_MODE_JOB list (skip blocks'
+    seg_idx already resolved).  check: raise where the reference's assert!s
+    would fire (check_mode_jobs); without it the device only counts such jobs.
+    Returns (tokens u32, offsets u32 [n + 1], rejected job count)."""
+    jobs = np.ascontiguousarray(jobs, EC_MODE_JOB)
+    if check:
+        check_mode_jobs(jobs, stack_mvs)
+    n = len(jobs)
+    dims = params.tile_dims
+    nt = len(dims)
+    mw = int(max(1, (dims[:, 0].max() + 1) // 2))
+    mh = int(max(1, (dims[:, 1].max() + 1) // 2))
+    dj = DeviceBuffer.from_array(jobs) if n else None
+    ddim = DeviceBuffer.from_array(dims)
+    dmap = DeviceBuffer(nt * mw * mh * 4)
+    scr = DeviceBuffer(lib().rv_ec_mode_scratch_bytes(n))
+    doff = DeviceBuffer(4 * (n + 1))
+    cap = 72 * n + 16
+    dtok = DeviceBuffer(4 * cap)
+    dst = DeviceBuffer(12)
+    _check(lib().rv_ec_mode_tokenize(dj.ptr if n else None, n, params.c_struct(), nt, ddim.ptr, mw,
+                                     mh, dmap.ptr, scr.ptr, doff.ptr, dtok.ptr, cap, dst.ptr,
+                                     None), "rv_ec_mode_tokenize")
+    _sync(None)
+    status = dst.download(np.uint32)
+    if status[1]:
+        raise Rav1eHipError("ec_tokenize_modes: token buffer overflow")
+    return (dtok.download(np.uint32)[:int(status[0])], doff.download(np.uint32)[:n + 1],
+            int(status[2]))
+
+
+def code_tile(mode_jobs, coeff_jobs, coeffs, coeff_after, params, cdf_init, xdec=1, ydec=1,
+              stack_mvs=None):
+    """One tile's payload symbols: every block's mode tokens (rv_ec_mode_tokenize)
+    followed by the coefficient tokens of its transform blocks (rv_ec_tokenize),
+    through the host range coder.  coeff_jobs: code_coefficients' rows of this
+    one tile (kind 1 / 2 rows carry no tokens but keep the contexts right);
+    coeff_after[k]: the index of the mode job whose tokens coefficient job k
+    follows (ascending).  cdf_init:
+    the combined table.  Returns (bytes, final CDFs, tokens)."""
+    mode_jobs = np.ascontiguousarray(mode_jobs, EC_MODE_JOB)
+    coeff_jobs = np.asarray(coeff_jobs, np.int64).reshape(-1, 10)
+    coeff_after = np.asarray(coeff_after, np.int64)
+    if len(coeff_after) != len(coeff_jobs) or (np.diff(coeff_after) < 0).any() or \
+            (len(coeff_after) and not 0 <= coeff_after.min() <= coeff_after.max() < len(mode_jobs)):
+        raise Rav1eHipError("code_tile: coeff_after must map every coefficient job to a mode job")
+    mtok, moff, bad = ec_tokenize_modes(mode_jobs, params, stack_mvs)
+    if bad:
+        raise Rav1eHipError(f"code_tile: {bad} mode jobs outside the tokenizer's restrictions")
+    if len(coeff_jobs):
+        tk = _EcTokens(coeff_jobs, coeffs, xdec, ydec, "code_tile")
+        ctok, coff = tk.tokens(), tk.offsets().astype(np.int64)
+    else:
+        ctok, coff = np.zeros(0, np.uint32), np.zeros(1, np.int64)
+    # the interleave as a gather: every piece's destination from the two offset arrays
+    nm, nc = len(mode_jobs), len(coeff_jobs)
+    mlen, clen = np.diff(moff.astype(np.int64)), np.diff(coff)
+    # pieces in stream order: mode job i, then the coefficient jobs with coeff_after == i
+    key = np.concatenate([2 * np.arange(nm), 2 * coeff_after + 1])
+    order = np.argsort(key, kind="stable")
+    lens = np.concatenate([mlen, clen])[order]
+    src0 = np.concatenate([moff[:nm].astype(np.int64), len(mtok) + coff[:nc]])[order]
+    dst0 = np.concatenate([[0], np.cumsum(lens)[:-1]]) if len(lens) else np.zeros(0, np.int64)
+    total = int(lens.sum())
+    idx = np.repeat(src0 - dst0, lens) + np.arange(total)
+    tok = np.concatenate([mtok, ctok])[idx]
+    cdf = np.array(cdf_init, np.uint16)
+    by = ec_code_stream(tok, cdf)
+    return by, cdf, tok
 
 
 def ec_rate_batch(tokens, offsets, group_first, cdfs, group_cdf=None, init=None):

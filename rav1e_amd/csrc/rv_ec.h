@@ -116,6 +116,14 @@ struct EcCounter {
     return ((bytes * 8 + (uint32_t)cnt + 10) << 3) - frac();
   }
 };
+// tokens (format in rv_ec.hip)
+__host__ __device__ inline uint32_t ec_sym(int off, int len, int s) {
+  return (uint32_t)off | ((uint32_t)len << 13) | ((uint32_t)s << 18);
+}
+__host__ __device__ inline uint32_t ec_raw(int b) { return 0x80000000u | (uint32_t)(b & 1); }
+__host__ __device__ inline uint32_t ec_edge(int off, int len, int s, int gather, int bsl) {
+  return ec_sym(off, len, s) | ((uint32_t)gather << 23) | ((uint32_t)bsl << 25);
+}
 // a token's fields and the test both counters and the encoder apply to it
 __host__ __device__ inline bool ec_token_ok(uint32_t t, int total, int &off, int &len, int &s) {
   off = (int)(t & 0x1FFF);
@@ -124,6 +132,9 @@ __host__ __device__ inline bool ec_token_ok(uint32_t t, int total, int &off, int
   return !(off + len > total || len < 2 || s >= len - 1);
 }
 
+// exclusive scan of v[0..n) in place (rv_ec.hip); v[n] and status[0] = the total
+void ec_scan(uint32_t *v, int n, const uint32_t *dn, uint32_t *bsum, uint32_t *status,
+             hipStream_t st);
 int ec_frame_tokens(const EcFrameArgs &a, const EcFrameBufs &b, hipStream_t st);
 // worst-case jobs of a group of nsb superblocks (8x8 leaves at 4:2:0 or
 // 64x64 leaves with four chroma transforms at 4:4:4)

@@ -26,6 +26,14 @@
 //   symbol  bits 0-12 CDF offset (u16 units, rv_ec_tables.h layout),
 //           bits 13-17 CDF length (nsymbs + 1), bits 18-22 symbol
 //   raw bit bit 31 set, bit 0 the bit (Writer::bit, bool at 16384)
+//   edge    the frame-edge partition symbol of write_partition
+//           (src/context.rs:2082-2108), only in the mixed streams of
+//           rv_ec_mode.hip: bits 0-22 as a symbol's (the partition CDF's
+//           offset and length, the symbol is_split), bits 23-24 the gather
+//           (1 partition_gather_vert_alike, 2 _horz_alike), bits 25-26 the
+//           block-size class bsl the reference hands the gather (which
+//           ignores it).  The 2-entry CDF is gathered from the adapting
+//           partition CDF when the token is coded; nothing adapts.
 #include <stdlib.h>
 #include <string.h>
 
@@ -33,6 +41,7 @@
 
 #include "rv_device.h"
 #include "rv_ec.h"
+#include "rv_ec_mode_tables.h"
 #include "rv_ec_tables.h"
 #include "rv_quant_tables.h"
 
@@ -40,11 +49,6 @@ namespace rv {
 
 constexpr int kEcPadHor = 4;  // TX_PAD_HOR (src/context.rs:253)
 constexpr int kEcLds = 36 * 36 + 16;  // levels of a coded 32x32 block + its pad
-
-__host__ __device__ inline uint32_t ec_sym(int off, int len, int s) {
-  return (uint32_t)off | ((uint32_t)len << 13) | ((uint32_t)s << 18);
-}
-__host__ __device__ inline uint32_t ec_raw(int b) { return 0x80000000u | (uint32_t)(b & 1); }
 
 __device__ inline int coded_w(int tx) { return tx == 4 ? 32 : 4 << tx; }
 __device__ inline int golomb_bits(uint32_t level) {  // write_golomb(level - 15): 2 len - 1 bits
@@ -752,56 +756,73 @@ struct EcWriter {  // WriterBase<WriterEncoder> (src/ec.rs:100-600)
   }
 };
 
-}  // namespace
-
-extern "C" {
-
-long rv_ec_code_tokens(const uint32_t *tok, size_t n, uint16_t *cdf, uint8_t *out, size_t cap) {
-  if (!tok && n) return rv_set_error(RV_EINVAL, "rv_ec_code_tokens: null tokens");
-  if (!cdf) return rv_set_error(RV_EINVAL, "rv_ec_code_tokens: null cdf");
-  EcWriter w;
-  w.pre.reserve(n / 4 + 64);
+// One stream through a writer W (EcWriter / EcCounter).  total: the size of
+// the CDF table the tokens index; Mixed: the edge-partition token is coded
+// (the combined table's streams), else bits 23-30 are not looked at.
+template <bool Mixed, class W>
+static bool ec_run_stream(W &w, const uint32_t *tok, size_t n, uint16_t *cdf, int total) {
   for (size_t i = 0; i < n; i++) {
     const uint32_t t = tok[i];
     if (t >> 31) {
       w.bit(t & 1);
-    } else {
-      int off, len, s;
-      if (!ec_token_ok(t, RV_EC_TOTAL, off, len, s))
-        return rv_set_error(RV_EINVAL, "rv_ec_code_tokens: bad token");
-      w.symbol_update((uint32_t)s, cdf + off, len);
+      continue;
     }
+    int off, len, s;
+    if (!ec_token_ok(t, total, off, len, s)) return false;
+    uint16_t *c = cdf + off;
+    const int gather = Mixed ? (int)((t >> 23) & 3) : 0;
+    if (gather) {
+      // partition_gather_vert_alike / _horz_alike (src/context.rs:1995-2057) of a
+      // 10-type partition CDF, then Writer::symbol against [x, 0]: no adaptation
+      if (gather > 2 || len != 11 || s > 1 || off < RV_ECM_PARTITION ||
+          off + len > RV_ECM_PARTITION + 20 * 11 || (off - RV_ECM_PARTITION) % 11)
+        return false;
+      static const int types[2][6] = {{2, 3, 4, 6, 7, 9}, {1, 3, 4, 5, 6, 8}};
+      uint16_t o = 32768;
+      for (int e : types[gather - 1]) o = (uint16_t)(o - (uint16_t)((e > 0 ? c[e - 1] : 32768) - c[e]));
+      const uint32_t x = (uint16_t)(32768 - o);
+      if (s == 0)
+        w.store(32768u, x, 2);
+      else
+        w.store(x, 0u, 1);
+      continue;
+    }
+    w.store(s > 0 ? c[s - 1] : 32768u, c[s], (uint32_t)(len - 1 - s));
+    update_cdf(c, len - 1, (uint32_t)s);
   }
+  return true;
+}
+
+static long ec_code(const uint32_t *tok, size_t n, uint16_t *cdf, uint8_t *out, size_t cap,
+                    int total, bool mixed, const char *null_tok, const char *null_cdf,
+                    const char *bad) {
+  if (!tok && n) return rv_set_error(RV_EINVAL, null_tok);
+  if (!cdf) return rv_set_error(RV_EINVAL, null_cdf);
+  EcWriter w;
+  w.pre.reserve(n / 4 + 64);
+  if (!(mixed ? ec_run_stream<true>(w, tok, n, cdf, total) : ec_run_stream<false>(w, tok, n, cdf, total)))
+    return rv_set_error(RV_EINVAL, bad);
   const size_t nb = w.finish();
   if (out && nb <= cap) w.bytes(out);
   return (long)nb;
 }
 
-long rv_ec_count_tokens(const uint32_t *tok, size_t n, uint16_t *cdf, uint32_t *state) {
-  if (!tok && n) return rv_set_error(RV_EINVAL, "rv_ec_count_tokens: null tokens");
-  if (!cdf) return rv_set_error(RV_EINVAL, "rv_ec_count_tokens: null cdf");
+static long ec_count(const uint32_t *tok, size_t n, uint16_t *cdf, uint32_t *state, int total,
+                     bool mixed, const char *null_tok, const char *null_cdf, const char *bad_state,
+                     const char *bad) {
+  if (!tok && n) return rv_set_error(RV_EINVAL, null_tok);
+  if (!cdf) return rv_set_error(RV_EINVAL, null_cdf);
   EcCounter w;
   if (state) {
     if (state[0] < 0x8000 || state[0] > 0xFFFF || state[1] > 0xFFFF)
-      return rv_set_error(RV_EINVAL, "rv_ec_count_tokens: bad state");
+      return rv_set_error(RV_EINVAL, bad_state);
     w.rng = state[0];
     w.cnt = (int16_t)state[1];
   }
   // the byte count enters the rate only through its growth: w counts from 0
   const long before = 8 * (long)w.cnt - (long)w.frac();
-  for (size_t i = 0; i < n; i++) {
-    const uint32_t t = tok[i];
-    if (t >> 31) {
-      w.bit(t & 1);
-    } else {
-      int off, len, s;
-      if (!ec_token_ok(t, RV_EC_TOTAL, off, len, s))
-        return rv_set_error(RV_EINVAL, "rv_ec_count_tokens: bad token");
-      uint16_t *c = cdf + off;
-      w.store(s > 0 ? c[s - 1] : 32768u, c[s], (uint32_t)(len - 1 - s));
-      update_cdf(c, len - 1, (uint32_t)s);
-    }
-  }
+  if (!(mixed ? ec_run_stream<true>(w, tok, n, cdf, total) : ec_run_stream<false>(w, tok, n, cdf, total)))
+    return rv_set_error(RV_EINVAL, bad);
   const long rate = 64 * (long)w.bytes + 8 * (long)w.cnt - (long)w.frac() - before;
   if (state) {
     state[0] = w.rng;
@@ -809,6 +830,32 @@ long rv_ec_count_tokens(const uint32_t *tok, size_t n, uint16_t *cdf, uint32_t *
     state[2] += w.bytes;
   }
   return rate;
+}
+
+}  // namespace
+
+extern "C" {
+
+long rv_ec_code_tokens(const uint32_t *tok, size_t n, uint16_t *cdf, uint8_t *out, size_t cap) {
+  return ec_code(tok, n, cdf, out, cap, RV_EC_TOTAL, false, "rv_ec_code_tokens: null tokens",
+                 "rv_ec_code_tokens: null cdf", "rv_ec_code_tokens: bad token");
+}
+
+long rv_ec_count_tokens(const uint32_t *tok, size_t n, uint16_t *cdf, uint32_t *state) {
+  return ec_count(tok, n, cdf, state, RV_EC_TOTAL, false, "rv_ec_count_tokens: null tokens",
+                  "rv_ec_count_tokens: null cdf", "rv_ec_count_tokens: bad state",
+                  "rv_ec_count_tokens: bad token");
+}
+
+long rv_ec_code_stream(const uint32_t *tok, size_t n, uint16_t *cdf_all, uint8_t *out, size_t cap) {
+  return ec_code(tok, n, cdf_all, out, cap, RV_EC_TOTAL_ALL, true, "rv_ec_code_stream: null tokens",
+                 "rv_ec_code_stream: null cdf", "rv_ec_code_stream: bad token");
+}
+
+long rv_ec_count_stream(const uint32_t *tok, size_t n, uint16_t *cdf_all, uint32_t *state) {
+  return ec_count(tok, n, cdf_all, state, RV_EC_TOTAL_ALL, true, "rv_ec_count_stream: null tokens",
+                  "rv_ec_count_stream: null cdf", "rv_ec_count_stream: bad state",
+                  "rv_ec_count_stream: bad token");
 }
 
 int rv_ec_default_cdf(int qctx, uint16_t *out) {
@@ -830,6 +877,50 @@ void rv_ec_reset_counts(uint16_t *cdf) {
                                {RV_EC_DC_SIGN, 6, 3},     {RV_EC_INTER_TX, 16, 17}};
   for (const auto &f : fam)
     for (int i = 0; i < f[1]; i++) cdf[f[0] + i * f[2] + f[2] - 1] = 0;
+}
+
+int rv_ec_cdf_total_all(void) { return RV_EC_TOTAL_ALL; }
+
+int rv_ec_default_cdf_all(int qctx, uint16_t *out) {
+  if (qctx < 0 || qctx > 3 || !out) return rv_set_error(RV_EINVAL, "rv_ec_default_cdf_all");
+  memcpy(out, RV_EC_DEFAULT_CDF[qctx], sizeof(RV_EC_DEFAULT_CDF[qctx]));
+  memcpy(out + RV_EC_TOTAL, RV_ECM_DEFAULT_CDF, sizeof(RV_ECM_DEFAULT_CDF));
+  return RV_OK;
+}
+
+// CDFContext::reset_counts over both parts.  The sliced CDFs keep their
+// counter where update_cdf leaves it: partition_cdf[0..4) in entry 4,
+// [16..20) in entry 8, uv_mode_cdf[0] in entry UV_INTRA_MODES - 1.
+void rv_ec_reset_counts_all(uint16_t *cdf) {
+  rv_ec_reset_counts(cdf);
+  for (int i = 0; i < 4; i++) {  // inter_tx_cdf[2][i][12], [3][i][2]: the sliced sets' counters
+    cdf[RV_EC_INTER_TX + (2 * 4 + i) * 17 + 12] = 0;
+    cdf[RV_EC_INTER_TX + (3 * 4 + i) * 17 + 2] = 0;
+  }
+  static const int fam[][3] = {{RV_ECM_KF_Y, 25, 14},         {RV_ECM_Y_MODE, 4, 14},
+                               {RV_ECM_CFL_SIGN, 1, 9},       {RV_ECM_CFL_ALPHA, 6, 17},
+                               {RV_ECM_NEWMV, 7, 3},          {RV_ECM_ZEROMV, 2, 3},
+                               {RV_ECM_REFMV, 6, 3},          {RV_ECM_SKIP, 3, 3},
+                               {RV_ECM_INTRA_INTER, 4, 3},    {RV_ECM_ANGLE_DELTA, 8, 8},
+                               {RV_ECM_COMP_MODE, 5, 3},      {RV_ECM_COMP_REF_TYPE, 5, 3},
+                               {RV_ECM_COMP_REF, 9, 3},       {RV_ECM_COMP_BWD_REF, 6, 3},
+                               {RV_ECM_SINGLE_REF, 18, 3},    {RV_ECM_DRL, 3, 3},
+                               {RV_ECM_COMPOUND_MODE, 8, 9},  {RV_ECM_MV_JOINTS, 1, 5},
+                               {RV_ECM_SEG, 3, 9}};
+  for (const auto &f : fam)
+    for (int i = 0; i < f[1]; i++) cdf[f[0] + i * f[2] + f[2] - 1] = 0;
+  for (int i = 0; i < 20; i++) cdf[RV_ECM_PARTITION + i * 11 + (i < 4 ? 4 : i < 16 ? 10 : 8)] = 0;
+  for (int i = 0; i < 13; i++) {
+    cdf[RV_ECM_UV_MODE + i * 15 + 13] = 0;
+    cdf[RV_ECM_UV_MODE + (13 + i) * 15 + 14] = 0;
+  }
+  static const int mvc[][3] = {{RV_ECM_MVC_CLASSES, 1, 12}, {RV_ECM_MVC_CLASS0_FP, 2, 5},
+                               {RV_ECM_MVC_FP, 1, 5},       {RV_ECM_MVC_SIGN, 1, 3},
+                               {RV_ECM_MVC_CLASS0_HP, 1, 3}, {RV_ECM_MVC_HP, 1, 3},
+                               {RV_ECM_MVC_CLASS0, 1, 3},   {RV_ECM_MVC_BITS, 10, 3}};
+  for (int k = 0; k < 2; k++)
+    for (const auto &f : mvc)
+      for (int i = 0; i < f[1]; i++) cdf[RV_ECM_MV_COMP + 69 * k + f[0] + i * f[2] + f[2] - 1] = 0;
 }
 
 size_t rv_ec_scratch_bytes(int n_jobs) {

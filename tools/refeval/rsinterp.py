@@ -458,6 +458,8 @@ class Parser:
                     break
             self.expect("}")
             return ("struct", segs, fields)
+        if len(segs) == 1 and name in ("true", "false"):  # a bool literal, not a binding
+            return ("lit", ("lit", name == "true"))
         if len(segs) == 1 and not name[0].isupper():
             if self.eat("@"):
                 return ("at", name, self.parse_pattern1())
