@@ -1905,22 +1905,12 @@ int lrf_rdo_launch(const rv_plane rec[3], const rv_plane src[3], const uint8_t *
   const bool c420 = g.xdec && g.ydec;
   a.p0 = 0;
   const dim3 grid64((unsigned)g.nsb, c420 ? 1 : 3), grid32((unsigned)g.nsb, 2);
-  // RAV1E_LRF_WIDE=0 (A/B): the 1024-lane, 135 KB workgroup for 64 x 64 units
-  static const bool wide = [] {
-    const char *e = getenv("RAV1E_LRF_WIDE");
-    return !(e && e[0] == '0');
-  }();
-  if (wide) {
-    if (rec[0].hbd)
-      lrf_rdo_wide_kernel<uint16_t><<<grid64, 512, 0, s>>>(a);
-    else
-      lrf_rdo_wide_kernel<uint8_t><<<grid64, 512, 0, s>>>(a);
-  } else {
-    if (rec[0].hbd)
-      lrf_rdo_kernel<uint16_t, 64, 64><<<grid64, 1024, 0, s>>>(a);
-    else
-      lrf_rdo_kernel<uint8_t, 64, 64><<<grid64, 1024, 0, s>>>(a);
-  }
+  // (tools/ubench/lrf_bench.hip still times lrf_rdo_kernel<Px, 64, 64>, the
+  // 1024-lane, 135 KB workgroup the wide kernel replaced)
+  if (rec[0].hbd)
+    lrf_rdo_wide_kernel<uint16_t><<<grid64, 512, 0, s>>>(a);
+  else
+    lrf_rdo_wide_kernel<uint8_t><<<grid64, 512, 0, s>>>(a);
   RV_HIP_CHECK_LAUNCH();
   if (c420) {
     a.p0 = 1;

@@ -117,7 +117,7 @@ struct DsArgs {
   // list-driven rounds: a listed job with dirty[job] == 0 keeps its result
   // (its inputs did not change; null: every listed job runs)
   const uint8_t *dirty;
-  // list-driven: the workgroup pool (0: ds_list_grid(); a round expected to
+  // list-driven: the workgroup pool (0: kDsListGrid; a round expected to
   // list most jobs, e.g. the first after round 0, asks for a full grid)
   int list_grid;
   // RAV1E_HIP_DS_PHASES=1 (diagnostic): list-driven sub-pel jobs add their
@@ -145,16 +145,7 @@ __device__ __forceinline__ int ds_list_job(const DsArgs &a, int ord) {
 // Workgroups of a list-driven launch: enough to cover a typical round's
 // superblocks at once, few enough that a near-empty round costs ~1 us of
 // dispatch (a full 4080-workgroup grid of early exits costs ~10 us).
-constexpr int kDsListGridDefault = 512;
-// RAV1E_HIP_DS_POOL (A/B): the list-driven launches' workgroup pool
-static int ds_list_grid() {
-  static const int g = [] {
-    const char *e = getenv("RAV1E_HIP_DS_POOL");
-    const int v = e ? atoi(e) : kDsListGridDefault;
-    return v > 0 ? v : kDsListGridDefault;
-  }();
-  return g;
-}
+constexpr int kDsListGrid = 512;
 
 __device__ __forceinline__ void ds_write(const DsArgs &a, int job, rv_mv center,
                                          uint64_t cost) {
@@ -736,8 +727,7 @@ __device__ __forceinline__ rv_mv ds_fast_body(const DsArgs &a, const int job, bo
 }
 
 // The 4-wavefront search at 5 waves per SIMD (<= 96 VGPRs: the u8 sub-pel
-// search fits without spilling), and at the compiler's choice
-// (RAV1E_HIP_DS_OCC4=1, A/B).
+// search fits without spilling).
 // The workgroup's jobs: one (xcd_job) on a full grid, or, list-driven, the
 // listed superblocks' jobs (every reference's) from blockIdx.x in steps of
 // the grid.  Every bound is uniform over the workgroup.
@@ -773,10 +763,6 @@ ds_fast_kernel(DsArgs a) {
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(a.t1, (unsigned long long)wall_clock64());
   }
-}
-template <typename Px, int W, int H, bool SUB>
-__global__ __launch_bounds__(kDsThreads) void ds_fast_kernel_occ4(DsArgs a) {
-  ds_fast_jobs<Px, W, H, SUB>(a);
 }
 
 // ============================ generic path =================================
@@ -1537,8 +1523,8 @@ bool try_grp(const DsArgs &a, hipStream_t s) {
   if (!(small || (a.satd && (n == 32 || n == 64)))) return false;
   const int jpw = 64 / (n == 8 || (n == 16 && !a.subpel && !a.satd) ? 16 : 64);
   unsigned grid = (unsigned)((a.n + 4 * jpw - 1) / (4 * jpw));
-  if (a.alist && grid > (unsigned)(a.list_grid ? a.list_grid : ds_list_grid()))
-    grid = (unsigned)(a.list_grid ? a.list_grid : ds_list_grid());
+  if (a.alist && grid > (unsigned)(a.list_grid ? a.list_grid : kDsListGrid))
+    grid = (unsigned)(a.list_grid ? a.list_grid : kDsListGrid);
 #define RV_GRP(N)                                                                     \
   if (n == N) {                                                                       \
     if (a.subpel) {                                                                   \
@@ -1561,30 +1547,15 @@ bool try_grp(const DsArgs &a, hipStream_t s) {
 // Blocks up to 32x32 take ds_wave_kernel (2160p F2, 32x32 at half
 // resolution: 0.031 -> 0.023 ms); 64x64 stays on the 4-wavefront kernel
 // (0.035 vs 0.037 ms: 16 row loads per round from one wavefront issue
-// slower than 4 from each of four).  RAV1E_HIP_DS_WG=1: always the
-// 4-wavefront kernel (A/B).
-static bool ds_full_wave() {
-  static const bool on = [] {
-    const char *e = getenv("RAV1E_HIP_DS_WG");
-    return !(e && e[0] == '1');
-  }();
-  return on;
-}
-
+// slower than 4 from each of four).
 template <typename Px, int W, int H, bool SUB>
 void launch_fast(DsArgs a, hipStream_t s) {
   static const bool phases = getenv("RAV1E_HIP_DS_PHASES") && getenv("RAV1E_HIP_DS_PHASES")[0] == '1';
   a.ph = phases && SUB && a.alist ? 1 : 0;
-  const unsigned grid = a.alist ? (unsigned)std::min(a.n, a.list_grid ? a.list_grid : ds_list_grid())
+  const unsigned grid = a.alist ? (unsigned)std::min(a.n, a.list_grid ? a.list_grid : kDsListGrid)
                                  : (unsigned)((a.n + 7) / 8 * 8);
-  static const bool occ4 = [] {
-    const char *e = getenv("RAV1E_HIP_DS_OCC4");
-    return e && e[0] == '1';
-  }();
-  if (!SUB && !a.tele && W * H <= 32 * 32 && ds_full_wave() && !a.alist)
+  if (!SUB && !a.tele && W * H <= 32 * 32 && !a.alist)
     ds_wave_kernel<Px, W, H><<<grid, 64, 0, s>>>(a);
-  else if (occ4)
-    ds_fast_kernel_occ4<Px, W, H, SUB><<<grid, kDsThreads, 0, s>>>(a);
   else
     ds_fast_kernel<Px, W, H, SUB><<<grid, kDsThreads, 0, s>>>(a);
 }
@@ -1708,7 +1679,7 @@ static void ds_fill(DsArgs &a, const rv_plane *org, const rv_plane *refs, int n_
 
 // A round's list-driven F2 (16x16 full-pel SAD on the half-resolution
 // planes) and F3 full-pel (64x64 SAD) in one launch (ds_f2_f3_kernel);
-// pools of list_grid workgroups each (0: ds_list_grid()).
+// pools of list_grid workgroups each (0: kDsListGrid).
 int rv_diamond_f2_f3(const rv_plane *org_h, const rv_plane *refs_h, const rv_ds_job *jobs_h,
                      rv_fs_result *out_h, const uint8_t *dirty_h, const rv_plane *org,
                      const rv_plane *refs, const rv_ds_job *jobs, rv_fs_result *out,
@@ -1735,7 +1706,7 @@ int rv_diamond_f2_f3(const rv_plane *org_h, const rv_plane *refs_h, const rv_ds_
   const int fuse = jobs_sub && out_sub ? 1 : 0;
   if (fuse) f3s.eval_acc = eval_acc;  // the kernel probe (null: off)
   unsigned long long *ts = fuse ? t01 : nullptr;
-  const int pool = list_grid ? list_grid : ds_list_grid();
+  const int pool = list_grid ? list_grid : kDsListGrid;
   const int g2 = std::min(pool, (f2.n + 15) / 16), g3 = std::min(f3.n, pool);
   hipStream_t s = rv_resolve_stream(stream);
   if (org->hbd)
@@ -1752,13 +1723,7 @@ static int ds_dispatch(DsArgs &a, void *stream) {
   const int n = a.n, blk_w = a.w, blk_h = a.h, subpixel = a.subpel;
   const rv_plane *org = &a.org;
   hipStream_t s = rv_resolve_stream(stream);
-  // RAV1E_HIP_DS_GENERIC=1: the workgroup-per-candidate kernel for SATD and
-  // the small blocks (A/B)
-  static const bool grp_on = [] {
-    const char *e = getenv("RAV1E_HIP_DS_GENERIC");
-    return !(e && e[0] == '1');
-  }();
-  const bool fast = (grp_on && (org->hbd ? try_grp<uint16_t>(a, s) : try_grp<uint8_t>(a, s))) ||
+  const bool fast = (org->hbd ? try_grp<uint16_t>(a, s) : try_grp<uint8_t>(a, s)) ||
                     (org->hbd ? try_fast<uint16_t>(a, s) : try_fast<uint8_t>(a, s));
   if (!fast) {
     const size_t lds = subpixel ? (size_t)((blk_w + 7) * (blk_h + 7) + (blk_h + 7) * blk_w +

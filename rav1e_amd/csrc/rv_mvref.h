@@ -63,19 +63,7 @@ struct MvrefArgs {
   // re-run; a listed superblock's other jobs keep their results
   uint8_t *f3dirty;
   uint8_t *f2dirty;  // out (null: none): per F2 job [R][nsb][4], 1 = its set changed
-  int field_guess_la;  // the first check: the EPZS field from the quadrants alone (A/B)
-  // An incremental check (plist non-null): only the superblocks whose inputs
-  // the previous round can have changed -- the right, below-left, below and
-  // below-right neighbours of every superblock the previous check listed
-  // (its list plist, *pcount entries): a superblock's stacks and EPZS sets
-  // read only its left, top-left, top and top-right neighbours (DESIGN.md
-  // §3).  epoch[sb] holds the tag of the last check that claimed sb (each
-  // candidate is checked once per check); tag > every earlier check's.
-  const int32_t *plist;
-  const int32_t *pcount;
-  uint32_t *epoch;
-  uint32_t tag;
-  int inc_grid;  // workgroups of the incremental check (0: the full check's)
+  int field_guess_la;  // always 0 (enc_field still reads it: a removed experiment)
 };
 
 // The decision record of superblock sb's winner (candidate c of the
@@ -106,12 +94,8 @@ __device__ inline BlkDec blk_dec_of(const CandGeo &cg, const rv_fs_result *sub, 
 
 }  // namespace rv
 
-// One round over the group's superblocks (the first marks every one); scan:
-// the tail rounds' predictive per-tile wavefront scan (its tile must fit
-// the 64 KiB of LDS a workgroup may take: RV_EINVAL otherwise).
-int rv_mvref_round(const rv::MvrefArgs &a, hipStream_t s, bool scan = false);
+// One round over the group's superblocks (the first marks every one).
+int rv_mvref_round(const rv::MvrefArgs &a, hipStream_t s);
 // The coded frame's field (the frame_mvs subset C of later frames reads) of
 // the group's part, into field ([h_in_b/2][w_in_b/2][R] rv_mv).
 int rv_mvref_field(const rv::MvrefArgs &a, rv_mv *field, hipStream_t s);
-// The largest tile (superblocks) the scan takes.
-constexpr int kMvrefScanMaxSb = (65536 - 1024) / (int)sizeof(rv::BlkDec);  // + the scan's static LDS

@@ -358,81 +358,11 @@ __global__ __launch_bounds__(256) void mvref_field_kernel(MvrefArgs a, rv_mv *fi
     field[((size_t)y8 * w8 + x8) * a.R + k] = enc_field(a, k, 2 * x8, 2 * y8, -1, -1);
 }
 
-// One check: 16 lanes per superblock -- lane 0 its stacks, lanes 1 .. 5 R
-// its EPZS jobs (F3 per reference, F2 per quadrant and reference) -- so a
-// superblock's eleven sets are built side by side.
-constexpr int kCheckLanes = 16;
-__global__ __launch_bounds__(256) void mvref_kernel(MvrefArgs a) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int sb = t / kCheckLanes, j = t % kCheckLanes;
-  const int lane = threadIdx.x & 63;
-  bool changed = false;
-  uint32_t pmask = 0;  // lane 0: the references whose rate predictors changed
-  const bool live = sb < a.nsb;
-  if (live) {
-    const int sx = sb % a.tw, sy = sb / a.tw;
-    const int fsx = a.tx0 + sx, fsy = a.ty0 + sy;  // frame superblock
-    if (j == 0) {
-      // the tile: its origin in superblocks and its size in 4x4 units
-      // (TileBlocks cols / rows, src/tiling/tiler.rs:194-202)
-      const int t0x = fsx - fsx % a.tws, t0y = fsy - fsy % a.ths;
-      const int cols = min(a.tws * 16, a.w_in_b - t0x * 16);
-      const int bx = (fsx - t0x) * 16, by = (fsy - t0y) * 16;  // tile-relative 4x4 offset
-      const int X = fsx * 64, Y = fsy * 64;
-      // a superblock past the frame edge is split (must_split): its 64x64 is
-      // evaluated but never coded, with empty stacks (and it reads no
-      // neighbour: the edge levels' winners may still be in flight)
-      const bool split = a.lvl && (X + 64 > a.W || Y + 64 > a.H);
-      Nb nb;
-      nb.up = !split && by > 0;
-      nb.left = !split && bx > 0;
-      nb.tr = !split && by > 0 && bx + 16 < cols;  // has_tr(64x64) && scan_blk_mbmi's bound
-      nb.tl = !split && bx > 0 && by > 0;
-      if (nb.up) nb.a = coded_at(a, sb - a.tw, X, Y - 4);
-      if (nb.left) nb.l = coded_at(a, sb - 1, X - 4, Y);
-      if (nb.tr) nb.r = coded_at(a, sb - a.tw + 1, X + 64, Y - 4);
-      if (nb.tl) nb.d = coded_at(a, sb - a.tw - 1, X - 4, Y - 4);
-      const MvStack s = stacks_of(a, nb, split, fsx, fsy);
-      changed = !same_stacks(a, a.stk[sb], s);
-#pragma unroll
-      for (int k = 0; k < 2; k++)
-        if (k < a.R && (a.init || !mv_eq(a.stk[sb].s[k][0], s.s[k][0]) ||
-                        !mv_eq(a.stk[sb].s[k][1], s.s[k][1])))
-          pmask |= 1u << k;
-      if (changed) set_stacks(a, sb, s);  // (its pmv: the F3 jobs' rate predictors)
-    } else if (a.epzs && j <= 5 * a.R) {
-      changed = epzs_job(a, sb, fsx, fsy, j - 1);
-    }
-  }
-  // the superblock's lanes: any change marks it (lane 0 records and lists it)
-  const uint64_t cm = __ballot(changed);
-  const int g0 = lane & ~(kCheckLanes - 1);
-  const uint32_t pm = (uint32_t)__shfl((int)pmask, g0, 64);
-  if (a.f3dirty && live && j >= 1 && j <= a.R)  // F3 job j - 1: its set or its pmv
-    a.f3dirty[(size_t)(j - 1) * a.nsb + sb] = (changed || ((pm >> (j - 1)) & 1)) ? 1 : 0;
-  if (a.f2dirty && live && j > a.R && j <= 5 * a.R) {  // F2 quadrant job (me_ss2's rate
-    const int e = j - 1 - a.R, k = e >> 2;             // predictor is the global MV: its set
-    a.f2dirty[((size_t)k * a.nsb + sb) * 4 + (e & 3)] = (changed || a.init) ? 1 : 0;  // alone)
-  }
-  const bool mark = live && ((cm >> g0) & ((1ull << kCheckLanes) - 1)) != 0;
-  const bool lead = live && j == 0;
-  if (lead) a.active[sb] = mark;
-  // wave-aggregated append to the list (the returned base orders the
-  // workgroup's adds before its ticket below)
-  const uint64_t m = __ballot(lead && mark);
-  int base = 0;
-  if (lane == 0 && m) base = atomicAdd(a.count, (int)__popcll(m));
-  base = __shfl(base, 0, 64);
-  if (lead && mark) a.list[base + __popcll(m & ((1ull << lane) - 1))] = sb;
-  round_publish(a.pub);
-}
-
-// The same check with one role per wavefront: a workgroup holds 64
-// superblocks, wavefront 0 their stacks and wavefront r (1 .. 5 R) their
-// EPZS job r - 1, so no wavefront runs two roles' code one after the other
-// (the 16-lane layout above executes the stack path and the EPZS path of
-// its lanes in turn, with their loads' latencies in series).  A
-// superblock's roles meet in LDS.
+// One check, one role per wavefront: a workgroup holds 64 superblocks,
+// wavefront 0 their stacks and wavefront r (1 .. 5 R) their EPZS job r - 1
+// (F3 per reference, F2 per quadrant and reference), so no wavefront runs
+// two roles' code one after the other with their loads' latencies in
+// series.  A superblock's roles meet in LDS.
 constexpr int kSplitSb = 64;
 // One role of superblock sb's check: role 0 its stacks (pmask: the
 // references whose rate predictors changed), role r its EPZS job r - 1.
@@ -440,7 +370,7 @@ constexpr int kSplitSb = 64;
 __device__ __forceinline__ bool check_role(const MvrefArgs &a, int sb, int role, uint32_t *pmask) {
   const int sx = sb % a.tw, sy = sb / a.tw;
   const int fsx = a.tx0 + sx, fsy = a.ty0 + sy;
-  if (role == 0) {  // the stacks (as in mvref_kernel's lane 0)
+  if (role == 0) {  // the stacks
     const int t0x = fsx - fsx % a.tws, t0y = fsy - fsy % a.ths;
     const int cols = min(a.tws * 16, a.w_in_b - t0x * 16);
     const int bx = (fsx - t0x) * 16, by = (fsy - t0y) * 16;
@@ -510,209 +440,12 @@ __global__ __launch_bounds__(1024) void mvref_split_kernel(MvrefArgs a) {
   check_finish(a, sb, role, sbl, live, chg[sbl], pmk[sbl]);
   round_publish(a.pub);
 }
-
-// The incremental check (a.plist): the same roles over the dependents of
-// the previous check's list, 64 candidates per workgroup pass; a candidate
-// is claimed once per check through epoch (the first claimant checks it).
-__global__ __launch_bounds__(1024) void mvref_inc_kernel(MvrefArgs a) {
-  __shared__ int32_t sbs[kSplitSb];
-  __shared__ uint32_t chg[kSplitSb];
-  __shared__ uint32_t pmk[kSplitSb];
-  const int role = (int)(rv_tid() >> 6), sbl = (int)(rv_tid() & 63);
-  const int items = 4 * __builtin_amdgcn_readfirstlane(*a.pcount);
-  for (int base = (int)blockIdx.x * kSplitSb; base < items; base += (int)gridDim.x * kSplitSb) {
-    if (role == 0) {
-      int s = -1;
-      const int it = base + sbl;
-      if (it < items) {
-        const int e = a.plist[it >> 2], d = it & 3;  // right, below-left, below, below-right
-        const int nx = e % a.tw + (d == 0 ? 1 : d - 2), ny = e / a.tw + (d == 0 ? 0 : 1);
-        if (nx >= 0 && nx < a.tw && ny < a.th) {
-          const int c = ny * a.tw + nx;
-          if (atomicMax(&a.epoch[c], a.tag) < a.tag) s = c;
-        }
-      }
-      sbs[sbl] = s;
-      chg[sbl] = pmk[sbl] = 0;
-    }
-    __syncthreads();
-    const int sb = sbs[sbl];
-    const bool live = sb >= 0;
-    if (live) {
-      uint32_t pm = 0;
-      const bool changed = check_role(a, sb, role, &pm);
-      if (role == 0) pmk[sbl] = pm;
-      if (changed) atomicOr(&chg[sbl], 1u << role);
-    }
-    __syncthreads();
-    check_finish(a, live ? sb : 0, role, sbl, live, chg[sbl], pmk[sbl]);
-    __syncthreads();  // the slot tables are rewritten by the next pass
-  }
-  round_publish(a.pub);
-}
-
-// A decision predicted under a new stack: the same candidate, its MVs taken
-// from the new stack (NEWMV keeps the last search's MV).  Only a guess that
-// lets a change run down a dependency chain in one round; the fixed point
-// does not depend on it.
-__device__ inline BlkDec predict(BlkDec d, const MvStack &s, int M, int R) {
-  if (d.cand == 255 || d.ref[0] == kIntraFrame) return d;
-  const int c = d.cand, ns = R * M;
-  if (c < ns) {
-    const int k = c / M, m = c - k * M;
-    if (m == kNearestMv) d.mv[0] = s.n[k] >= 1 ? s.s[k][0] : rv_mv{0, 0};
-    if (m == kNear0Mv && s.n[k] >= 1) d.mv[0] = s.n[k] >= 2 ? s.s[k][1] : rv_mv{0, 0};
-    return d;
-  }
-  switch (c - ns) {
-    case kNearestNearest: d.mv[0] = s.c[0][0]; d.mv[1] = s.c[0][1]; break;
-    case kNearNear: d.mv[0] = s.c[1][0]; d.mv[1] = s.c[1][1]; break;
-    case kNearestNew: d.mv[0] = s.c[0][0]; break;
-    case kNewNearest: d.mv[1] = s.c[0][1]; break;
-    default: break;
-  }
-  return d;
-}
-
-// The tail rounds (few superblocks still changing, mostly along dependency
-// chains): one workgroup per tile scans its superblocks in anti-diagonal
-// wavefronts (x + 2 y = d: the left, above, top-right and top-left
-// neighbours lie on earlier ones).  A superblock whose stack and EPZS sets
-// held keeps its evaluated decision; one whose stack changed is marked and,
-// for the superblocks after it, predicted (the same candidate under the new
-// stack), so a chain of changes is evaluated in one round when the
-// predictions hold.  The EPZS sets read the field of those (predicted)
-// decisions, or the quadrant results.  The tile's decisions live in LDS.
-// Per wavefront: (A) one thread per superblock, its stacks; (B) one thread
-// per (superblock, EPZS job); (C) one thread per superblock, the mark.
-constexpr int kScanThreads = 256, kScanMaxDiag = 64;
-__global__ __launch_bounds__(kScanThreads) void mvref_scan_kernel(MvrefArgs a) {
-  extern __shared__ BlkDec pd[];
-  __shared__ uint8_t smark[kScanMaxDiag], sch[kScanMaxDiag];
-  __shared__ uint32_t spm[kScanMaxDiag];
-  const int gtx = (a.tw + a.tws - 1) / a.tws;
-  const int lx0 = (int)(blockIdx.x % gtx) * a.tws, ly0 = (int)(blockIdx.x / gtx) * a.ths;
-  const int twd = min(a.tws, a.tw - lx0), tht = min(a.ths, a.th - ly0);
-  const int ndiag = (twd - 1) + 2 * (tht - 1) + 1;
-  const int t0x = a.tx0 + lx0, t0y = a.ty0 + ly0;
-  const int cols = min(a.tws * 16, a.w_in_b - t0x * 16);
-  const int nj = a.epzs ? 5 * a.R : 0;  // EPZS jobs per superblock
-  auto is_split = [&](int SX, int SY) { return a.lvl && ((SX + 1) * 64 > a.W || (SY + 1) * 64 > a.H); };
-  __syncthreads();
-  for (int d = 0; d < ndiag; d++) {
-    const int ylo = max(0, (d - twd + 2) / 2), yhi = min(tht - 1, d / 2);
-    const int nd = yhi - ylo + 1;  // superblocks on this wavefront (<= kScanMaxDiag)
-    // (A) stacks
-    for (int i = (int)threadIdx.x; i < nd; i += kScanThreads) {
-      const int y = ylo + i, x = d - 2 * y;
-      const int sb = (ly0 + y) * a.tw + lx0 + x;
-      const int fsx = t0x + x, fsy = t0y + y;
-      const int X = fsx * 64, Y = fsy * 64, bx = x * 16, by = y * 16;
-      const bool split = is_split(fsx, fsy);
-      // a neighbour: LDS (this tile), or a must_split leaf
-      auto nbr = [&](int nx, int ny, int PX, int PY) -> BlkDec {
-        if (is_split(t0x + nx, t0y + ny)) return coded_at(a, 0, PX, PY);
-        BlkDec v = pd[ny * twd + nx];
-        if (a.iwas && a.iwas[(ly0 + ny) * a.tw + lx0 + nx]) v.ref[0] = kIntraFrame, v.ref[1] = kNoneFrame;
-        return v;
-      };
-      Nb nb;
-      nb.up = !split && by > 0;
-      nb.left = !split && bx > 0;
-      nb.tr = !split && by > 0 && bx + 16 < cols;
-      nb.tl = !split && bx > 0 && by > 0;
-      if (nb.up) nb.a = nbr(x, y - 1, X, Y - 4);
-      if (nb.left) nb.l = nbr(x - 1, y, X - 4, Y);
-      if (nb.tr) nb.r = nbr(x + 1, y - 1, X + 64, Y - 4);
-      if (nb.tl) nb.d = nbr(x - 1, y - 1, X - 4, Y - 4);
-      const MvStack st = stacks_of(a, nb, split, fsx, fsy);
-      const bool mark = !same_stacks(a, a.stk[sb], st);
-      uint32_t pm = 0;
-#pragma unroll
-      for (int k = 0; k < 2; k++)
-        if (k < a.R && (!mv_eq(a.stk[sb].s[k][0], st.s[k][0]) ||
-                        !mv_eq(a.stk[sb].s[k][1], st.s[k][1])))
-          pm |= 1u << k;
-      const BlkDec cur = a.dec[sb];
-      if (mark) set_stacks(a, sb, st);
-      pd[y * twd + x] = mark ? predict(cur, st, kCandModes, a.R) : cur;
-      smark[i] = mark;
-      sch[i] = 0;
-      spm[i] = pm;
-    }
-    __syncthreads();
-    // (B) the EPZS sets, the field from the tile's (predicted) decisions
-    for (int t = (int)threadIdx.x; t < nd * nj; t += kScanThreads) {
-      const int i = t / nj, j = t - i * nj;
-      const int y = ylo + i, x = d - 2 * y;
-      const int sb = (ly0 + y) * a.tw + lx0 + x;
-      const int fsx = t0x + x, fsy = t0y + y;
-      auto fld = [&](int k, int X4, int Y4) -> rv_mv {
-        const int SX = X4 >> 4, SY = Y4 >> 4;
-        if (SX == fsx && SY == fsy) return rv_mv{0, 0};  // its own quadrants: after its F2
-        const int gsb = (SY - a.ty0) * a.tw + (SX - a.tx0);
-        const int lx = SX - t0x, ly = SY - t0y;
-        BlkDec dd;
-        dd.ref[0] = kIntraFrame;
-        if (is_split(SX, SY)) {
-          if (a.edge_ok) dd = coded_at(a, gsb, X4 * 4, Y4 * 4);
-        } else if (lx >= 0 && lx < twd && ly >= 0 && ly < tht) {
-          dd = pd[ly * twd + lx];
-          if (a.iwas && a.iwas[gsb]) dd.ref[0] = kIntraFrame;
-        } else {
-          dd = coded_at(a, gsb, X4 * 4, Y4 * 4);
-        }
-        if (dd.ref[0] != kIntraFrame && dd.ref[0] - 1 == k) return dd.mv[0];
-        const rv_mv h = a.hq[((size_t)k * a.nsb + gsb) * 4 + ((Y4 >> 3) & 1) * 2 + ((X4 >> 3) & 1)].best_mv;
-        return rv_mv{(int16_t)(h.row * 2), (int16_t)(h.col * 2)};
-      };
-      const bool ch = epzs_job_f(a, sb, fsx, fsy, j, fld);
-      if (ch) sch[i] = 1;  // (any writer)
-      if (j < a.R) {
-        if (a.f3dirty) a.f3dirty[(size_t)j * a.nsb + sb] = (ch || ((spm[i] >> j) & 1)) ? 1 : 0;
-      } else if (a.f2dirty) {
-        const int e = j - a.R;
-        a.f2dirty[((size_t)(e >> 2) * a.nsb + sb) * 4 + (e & 3)] = ch ? 1 : 0;
-      }
-    }
-    __syncthreads();
-    // (C) the mark (a superblock marked by its sets alone keeps its decision)
-    for (int i = (int)threadIdx.x; i < nd; i += kScanThreads) {
-      const int y = ylo + i, x = d - 2 * y;
-      const int sb = (ly0 + y) * a.tw + lx0 + x;
-      const bool mark = smark[i] || sch[i];
-      a.active[sb] = mark;
-      if (!a.epzs && a.f3dirty)
-        for (int k = 0; k < a.R; k++) a.f3dirty[(size_t)k * a.nsb + sb] = (spm[i] >> k) & 1;
-      if (mark) a.list[atomicAdd(a.count, 1)] = sb;  // the returned index orders it before the ticket
-    }
-    __syncthreads();  // the wavefront's decisions before the next one reads them
-  }
-  round_publish(a.pub);
-}
 }  // namespace
 
-int rv_mvref_round(const MvrefArgs &a, hipStream_t s, bool scan) {
+int rv_mvref_round(const MvrefArgs &a, hipStream_t s) {
   if (a.nsb <= 0) return RV_OK;
-  // RAV1E_HIP_CHECK_SPLIT=0: the 16-lane check (A/B)
-  static const bool check_split = !(getenv("RAV1E_HIP_CHECK_SPLIT") && getenv("RAV1E_HIP_CHECK_SPLIT")[0] == '0');
-  // the scan: a tile's decisions in LDS, at most kScanMaxDiag superblocks
-  // per wavefront; otherwise the Jacobi check
-  const bool scan_ok = a.tws * a.ths <= kMvrefScanMaxSb && (a.ths < a.tws ? a.ths : a.tws) <= kScanMaxDiag;
-  if (scan && !a.init && scan_ok) {
-    const int ntiles = ((a.tw + a.tws - 1) / a.tws) * ((a.th + a.ths - 1) / a.ths);
-    mvref_scan_kernel<<<ntiles, kScanThreads, (size_t)a.tws * a.ths * sizeof(BlkDec), s>>>(a);
-  } else if (check_split && a.plist && a.epoch) {
-    const int nr = 1 + (a.epzs ? 5 * a.R : 0);
-    const int full = (a.nsb + kSplitSb - 1) / kSplitSb;
-    const int grid = a.inc_grid > 0 ? std::min(a.inc_grid, full) : full;
-    mvref_inc_kernel<<<grid, kSplitSb * nr, 0, s>>>(a);
-  } else if (check_split) {
-    const int nr = 1 + (a.epzs ? 5 * a.R : 0);
-    mvref_split_kernel<<<(a.nsb + kSplitSb - 1) / kSplitSb, kSplitSb * nr, 0, s>>>(a);
-  } else {
-    mvref_kernel<<<(a.nsb * kCheckLanes + 255) / 256, 256, 0, s>>>(a);
-  }
+  const int nr = 1 + (a.epzs ? 5 * a.R : 0);
+  mvref_split_kernel<<<(a.nsb + kSplitSb - 1) / kSplitSb, kSplitSb * nr, 0, s>>>(a);
   RV_HIP_CHECK_LAUNCH();
   return RV_OK;
 }

@@ -1181,7 +1181,7 @@ struct QuadPh {
   unsigned long long t[5];
 };
 
-// var (RAV1E_HIP_RDO_VARIANT, A/B): bit 0 moves the skip distortion of the
+// var (the host passes kRdoVariant, both bits): bit 0 moves the skip distortion of the
 // scoring launches into the narrow phases (waves 1..3 during the row DCT,
 // wave 2 for wave 0's candidate during the inverse rows); bit 1 raises the
 // priority of the waves running a narrow phase (s_setprio).
@@ -1326,22 +1326,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
   rdo_quad_wg<Px, MODE>(luma, chroma, nquads, var, blockIdx.x, lds, scan);
 }
 
-// The single-reference (MODE 0) and the compound (MODE 1) candidates of a
-// frame in one launch: workgroups below g0 run the single ones, the rest the
-// compound ones.  They are independent, and in the MV-stack rounds each
-// launch holds a few dozen superblocks' candidates, so two launches in a row
-// cost two candidate latencies where one costs one.
-template <typename Px>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void rdo_quad_pair_kernel(
-    RdoArgs l0, RdoArgs c0, int nq0, int g0, RdoArgs l1, RdoArgs c1, int nq1, int var) {
-  __shared__ __align__(16) uint8_t lds[QuadLds<Px>::kBytes];
-  __shared__ uint16_t scan[1024];
-  if ((int)blockIdx.x < g0)
-    rdo_quad_wg<Px, 0>(l0, c0, nq0, var, blockIdx.x, lds, scan);
-  else
-    rdo_quad_wg<Px, 1>(l1, c1, nq1, var, blockIdx.x - g0, lds, scan);
-}
-
 // List-driven score launches (the compacted candidate lists of round 0 and of
 // every MV-stack round): a pool of workgroups walks the live work only.  The
 // device counts give the live luma quads and chroma triples of set A (MODE
@@ -1435,17 +1419,12 @@ __global__ __launch_bounds__(256) void rdo_args_store_kernel(RdoArgs a0, RdoArgs
   }
 }
 
-// The pool of a list-driven launch: RAV1E_HIP_F4_POOL workgroups (default
-// 1024, four per CU: the LDS of QuadLds allows four), never more than the
-// full grid.
-static int rdo_f4_pool() {
-  static const int pool = [] {
-    const char *e = getenv("RAV1E_HIP_F4_POOL");
-    const int v = e ? atoi(e) : 1024;
-    return v > 0 ? v : 1024;
-  }();
-  return pool;
-}
+// The pool of a list-driven launch (workgroups): four per CU (the LDS of
+// QuadLds allows four), never more than the full grid.
+constexpr unsigned kF4Pool = 1024;
+// rdo_quad_luma's var, bits 0 (late_dist) and 1 (prio): both (measured at
+// 2160p: 880 vs 850 frames/s, r03g)
+constexpr int kRdoVariant = 3;
 
 }  // namespace rv
 
@@ -1546,13 +1525,8 @@ static void rdo_small_launch(const RdoArgs &a, int nplanes, int hbd, hipStream_t
 
 template <int MODE>
 static void rdo_launch(const RdoArgs &luma, const RdoArgs &chroma, int hbd, hipStream_t s,
-                       bool single, unsigned cpairs) {
-  // default 3: both (measured at 2160p: 880 vs 850 frames/s, r03g)
-  static const int var = [] {
-    const char *e = getenv("RAV1E_HIP_RDO_VARIANT");
-    return e ? atoi(e) : 3;
-  }();
-  if (luma.bd == 12 || single) {  // 12-bit: i32 row-pass intermediate
+                       unsigned cpairs) {
+  if (luma.bd == 12) {  // 12-bit: i32 row-pass intermediate, one candidate per workgroup
     const unsigned grid = (unsigned)luma.n_tx + cpairs;
     if (grid == 0) return;
     if (hbd)
@@ -1565,9 +1539,9 @@ static void rdo_launch(const RdoArgs &luma, const RdoArgs &chroma, int hbd, hipS
   const unsigned grid = (unsigned)nquads + (cpairs + 2) / 3;
   if (grid == 0) return;
   if (hbd)
-    rdo_quad_kernel<uint16_t, MODE><<<grid, 256, 0, s>>>(luma, chroma, nquads, var);
+    rdo_quad_kernel<uint16_t, MODE><<<grid, 256, 0, s>>>(luma, chroma, nquads, kRdoVariant);
   else
-    rdo_quad_kernel<uint8_t, MODE><<<grid, 256, 0, s>>>(luma, chroma, nquads, var);
+    rdo_quad_kernel<uint8_t, MODE><<<grid, 256, 0, s>>>(luma, chroma, nquads, kRdoVariant);
 }
 
 // Replay-internal entry (rv_replay.hip): luma (N = 64, cdef distortion)
@@ -1576,46 +1550,12 @@ static void rdo_launch(const RdoArgs &luma, const RdoArgs &chroma, int hbd, hipS
 int rv_rdo_candidates(const RdoArgs &luma, const RdoArgs &chroma, int hbd, hipStream_t s,
                       bool compound) {
   const unsigned cpairs = (unsigned)(2 * ((chroma.n_tx + 1) / 2));
-  // RAV1E_HIP_RDO_SINGLE=1: one candidate per workgroup at every bit depth
-  static const bool single = [] {
-    const char *e = getenv("RAV1E_HIP_RDO_SINGLE");
-    return e && e[0] == '1';
-  }();
   if (luma.commit)
-    rdo_launch<2>(luma, chroma, hbd, s, single, cpairs);
+    rdo_launch<2>(luma, chroma, hbd, s, cpairs);
   else if (compound)
-    rdo_launch<1>(luma, chroma, hbd, s, single, cpairs);
+    rdo_launch<1>(luma, chroma, hbd, s, cpairs);
   else
-    rdo_launch<0>(luma, chroma, hbd, s, single, cpairs);
-  RV_HIP_CHECK_LAUNCH();
-  return RV_OK;
-}
-
-// The single-reference and the compound candidates in one launch
-// (rdo_quad_pair_kernel); the 12-bit and RAV1E_HIP_RDO_SINGLE paths launch
-// them one after the other.
-int rv_rdo_candidates_pair(const RdoArgs &l0, const RdoArgs &c0, const RdoArgs &l1,
-                           const RdoArgs &c1, int hbd, hipStream_t s) {
-  static const bool single = [] {
-    const char *e = getenv("RAV1E_HIP_RDO_SINGLE");
-    return e && e[0] == '1';
-  }();
-  if (l0.bd == 12 || single || l0.commit) {
-    const int rc = rv_rdo_candidates(l0, c0, hbd, s, false);
-    return rc != RV_OK ? rc : rv_rdo_candidates(l1, c1, hbd, s, true);
-  }
-  static const int var = [] {
-    const char *e = getenv("RAV1E_HIP_RDO_VARIANT");
-    return e ? atoi(e) : 3;
-  }();
-  const unsigned cp0 = (unsigned)(2 * ((c0.n_tx + 1) / 2)), cp1 = (unsigned)(2 * ((c1.n_tx + 1) / 2));
-  const int nq0 = (l0.n_tx + 3) / 4, nq1 = (l1.n_tx + 3) / 4;
-  const unsigned g0 = (unsigned)nq0 + (cp0 + 2) / 3, g1 = (unsigned)nq1 + (cp1 + 2) / 3;
-  if (g0 + g1 == 0) return RV_OK;
-  if (hbd)
-    rdo_quad_pair_kernel<uint16_t><<<g0 + g1, 256, 0, s>>>(l0, c0, nq0, (int)g0, l1, c1, nq1, var);
-  else
-    rdo_quad_pair_kernel<uint8_t><<<g0 + g1, 256, 0, s>>>(l0, c0, nq0, (int)g0, l1, c1, nq1, var);
+    rdo_launch<0>(luma, chroma, hbd, s, cpairs);
   RV_HIP_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -1636,21 +1576,17 @@ int rv_rdo_candidates_list(const RdoArgs *h, const RdoArgs *dev, int nsets, int 
   for (int k = 0; k < 2 * nsets; k++)
     if (!h[k].list || !h[k].count)
       return rv_set_error(RV_EINVAL, "rv_rdo_candidates_list: the sets must be list-driven");
-  static const int var0 = [] {
-    const char *e = getenv("RAV1E_HIP_RDO_VARIANT");
-    return e ? atoi(e) : 3;
-  }();
   static const bool phases = getenv("RAV1E_HIP_RDO_PHASES") && getenv("RAV1E_HIP_RDO_PHASES")[0] == '1';
-  // RAV1E_HIP_F4_CHROMA4=0: the rounds' chroma two blocks per wavefront (A/B)
-  static const bool chroma4 = !(getenv("RAV1E_HIP_F4_CHROMA4") && getenv("RAV1E_HIP_F4_CHROMA4")[0] == '0');
-  const int var = var0 | (phases && max_grid > 0 ? 16 : 0) | (chroma4 && max_grid > 0 ? 32 : 0);
+  // var bit 4: the phase clocks; bit 5: a sized round's chroma four blocks per
+  // workgroup (rdo_quad_chroma4) instead of three pairs
+  const int var = kRdoVariant | (phases && max_grid > 0 ? 16 : 0) | (max_grid > 0 ? 32 : 0);
   // the full grid (every listed slot live) bounds the pool
   unsigned full = 0;
   for (int k = 0; k < nsets; k++)
     full += (unsigned)((h[2 * k].n_tx + 3) / 4) +
             ((var & 32) ? (unsigned)(2 * h[2 * k + 1].n_tx + 3) / 4
                         : (unsigned)(2 * ((h[2 * k + 1].n_tx + 1) / 2) + 2) / 3);
-  unsigned grid = std::min(full, (unsigned)rdo_f4_pool());
+  unsigned grid = std::min(full, kF4Pool);
   if (max_grid > 0) grid = std::min(grid, (unsigned)max_grid);
   if (grid == 0) return RV_OK;
 #define RV_LIST(PX, MA, MB) \
@@ -1667,7 +1603,7 @@ int rv_rdo_candidates_list(const RdoArgs *h, const RdoArgs *dev, int nsets, int 
 
 int rv_rdo_intra(const RdoArgs &luma, const RdoArgs &chroma, int hbd, hipStream_t s) {
   const unsigned cpairs = (unsigned)(2 * ((chroma.n_tx + 1) / 2));
-  rdo_launch<3>(luma, chroma, hbd, s, false, cpairs);
+  rdo_launch<3>(luma, chroma, hbd, s, cpairs);
   RV_HIP_CHECK_LAUNCH();
   return RV_OK;
 }

@@ -1052,12 +1052,7 @@ struct RvLaEngine {
   static constexpr int kLaSlack = 28;
   int W = 0, RW = 0, dev = 0;
   long limit = 0;  // coded frames in the stream (0: unbounded)
-  hipStream_t las = nullptr;
-  // the window passes' stream (split): frame m's searches on las overlap
-  // window m - W's propagation (they share only the entries' lists, handed
-  // over with ev_lists); null: everything on las (the default; RAV1E_HIP_LA_SPLIT=1)
-  hipStream_t lap = nullptr;
-  bool split = false;
+  hipStream_t las = nullptr;  // the engine's stream: the searches and the window passes
   RoundRing rr;
   int32_t *la_list = nullptr;
   void *scratch = nullptr;
@@ -1071,7 +1066,6 @@ struct RvLaEngine {
     LaRefs lr{};
     hipEvent_t ev_imp = nullptr, ev_used = nullptr;
     hipEvent_t ev_data = nullptr, ev_xchg = nullptr;  // RCCL parts: data in / exchanged
-    hipEvent_t ev_lists = nullptr;  // split: the frame's lists are built (las -> lap)
   };
   std::vector<Entry> ring;
   std::vector<long> pyr_display;  // per input: the display whose pyramid it holds
@@ -1113,7 +1107,7 @@ struct rv_replay {
   hipStream_t stream;
   // FL runs on a second stream, overlapping F3/F4 (it only needs F1/F2's
   // MVs; score_candidates and F5 join it).  RAV1E_HIP_REPLAY_SERIAL=1: one
-  // stream (A/B).
+  // stream (the profiling mode).
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   hipEvent_t ev_ielig = nullptr;  // intra_begin's count is on the host
@@ -1155,7 +1149,7 @@ struct rv_replay {
   bool lv_used[kLevels] = {false, false, false, false};
   bool lv_me[kLevels] = {false, false, false, false};
   // speed 10: the edge levels run on their own stream beside the 64x64 stages
-  hipStream_t edge[kLevels] = {nullptr, nullptr, nullptr, nullptr};  // [1..3]: one per level
+  hipStream_t edge[kLevels] = {nullptr, nullptr, nullptr, nullptr};  // [1..3]: one stream, shared
   hipEvent_t ev_efork = nullptr, ev_l1me = nullptr, ev_epart = nullptr;
   hipEvent_t ev_ejoin[kLevels] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_ecommit[kLevels] = {nullptr, nullptr, nullptr, nullptr};
@@ -1172,10 +1166,6 @@ struct rv_replay {
   bool lrf = false;
   uint64_t *lrf_err = nullptr;
   int8_t *lrf_xqd = nullptr, *lrf_units = nullptr;
-  // the decision's side stream (RAV1E_LRF_SIDE=1; default: the replay stream)
-  hipStream_t lrf_side = nullptr;
-  hipEvent_t ev_lrf0 = nullptr, ev_lrf1 = nullptr;
-  bool lrf_pending = false;
   int lrf_fix_passes = 1 << 30;  // the decision kernel (create: RAV1E_LRF_FIX[_PASSES])
   RvInput lrf_out;
   RvInput cdef_pre;                 // the deblocked, pre-CDEF frame (the padded copy's source)
@@ -1188,11 +1178,6 @@ struct rv_replay {
   EcFrameBufs ecb{};
   EcHost *ech = nullptr;
   long ec_frames = 0;
-  // F8 runs on its own stream after the frame's block map, beside F7 and the
-  // next frame's F0..F4; the next commit (F6) waits for it
-  hipStream_t ecs = nullptr;
-  hipEvent_t ev_f8fork = nullptr, ev_f8done = nullptr;
-  bool f8_pending = false;
   // intra-mode screening (rv_intra_pass.hip; speed 10, 4:2:0)
   bool intra = false;
   uint8_t *i_elig = nullptr, *i_was = nullptr, *i_win = nullptr, *i_modes = nullptr;
@@ -1212,18 +1197,7 @@ struct rv_replay {
   static constexpr int kRoundsAhead = 2;  // rounds queued beyond the last count read
   RoundRing rr;
   int32_t *mv_list = nullptr;          // [2][nsb]: check q lists into half q & 1
-  uint32_t *mv_epoch = nullptr;        // [nsb]: the incremental checks' claims (MvrefArgs::epoch)
   bool edge_tr = false;                // a stack reads a frame-edge leaf (top-right)
-  // RAV1E_HIP_MV_HP=1: the rounds after the first on a high-priority stream
-  hipStream_t hp = nullptr;
-  hipEvent_t ev_hp0 = nullptr, ev_hp1 = nullptr;
-  // RAV1E_HIP_ROUND_FORK=1: a round's independent launches on a second
-  // stream (F2 beside F3, the compound F4 beside the single-reference one).
-  // Off: 2160p A/B 144-148 vs 164-165 fps (r04q) -- with the twin and the
-  // lookahead engine the process already has more streams than hardware
-  // queues, and the fork's events cost more than the overlap gains
-  hipStream_t rs2 = nullptr;
-  hipEvent_t ev_rfork = nullptr, ev_rlists = nullptr, ev_rjoin = nullptr;
   // evaluation rounds (round 0 included), re-evaluated superblocks and
   // round runs (1 + the MV / intra passes) per frame, summed
   long mv_round_sum = 0, mv_reeval = 0, mv_run_sum = 0;
@@ -1254,7 +1228,6 @@ struct rv_replay {
   CandKey *cand_key = nullptr;       // F4: what each candidate slot was last evaluated with
   uint8_t *f3dirty = nullptr;        // rounds: the F3 jobs whose set / pmv changed [R][nsb]
   uint8_t *f2dirty = nullptr;        // rounds: the F2 jobs whose set changed [R][nsb][4]
-  bool cand_reuse = true;            // a round keeps the F4 outputs of an unchanged candidate
   uint32_t *cand_evals;  // [kRing][2 * kLevels]: F4 candidates per frame and level (single, compound)
   int32_t *l_lev, *c_lev;   // F6: committed levels
   uint64_t *words;
@@ -1798,10 +1771,6 @@ int cdef_pad_slot(rv_replay *r, const RvSlot &s, int lv, const LrfGeo *lg) {
   // lrf_filter_frame: the CDEF output restored, the deblocked slot for the
   // stripes' edges (pre_cdef_frame, src/encoder.rs:2795-2806)
   const rv_plane lo[3] = {r->lrf_out.y, r->lrf_out.u, r->lrf_out.v};
-  if (r->lrf_pending) {  // the units of the side stream's decision
-    RV_H(hipStreamWaitEvent(r->stream, r->ev_lrf1, 0));
-    r->lrf_pending = false;
-  }
   RV_R(lrf_filter_launch(out, rec, lo, *lg, r->lrf_units, 1, r->stream));
   return rv_frame_pad_dev(rec, lo, r->stream);
 }
@@ -1821,16 +1790,7 @@ static int lrf_decide_slot(rv_replay *r, const RvSlot &s, const RvInput &in, int
   RV_R(lrf_rdo_launch(rec, src, r->mi_skip, r->mi_stride, r->imp_last, g.w_imp, g.w_in_b, g.h_in_b, lg,
                       r->cdef, r->cdef_dir, r->cdef_var, r->cdef_str[lv], r->lv[lv].ds, r->lrf_err,
                       r->lrf_xqd, rect, r->stream));
-  if (rect || !r->lrf_side)  // a group's units are packed right after: no overlap
-    return lrf_decide_launch(lg, r->lrf_err, r->lrf_xqd, r->lv[lv].lambda, r->lrf_units, rect, r->lrf_fix_passes, r->stream);
-  // the sequential decision (a few waves, latency only) on the side stream,
-  // beside the deblocking and CDEF; lrf_filter_launch waits for it
-  RV_H(hipEventRecord(r->ev_lrf0, r->stream));
-  RV_H(hipStreamWaitEvent(r->lrf_side, r->ev_lrf0, 0));
-  RV_R(lrf_decide_launch(lg, r->lrf_err, r->lrf_xqd, r->lv[lv].lambda, r->lrf_units, rect, r->lrf_fix_passes, r->lrf_side));
-  RV_H(hipEventRecord(r->ev_lrf1, r->lrf_side));
-  r->lrf_pending = true;
-  return RV_OK;
+  return lrf_decide_launch(lg, r->lrf_err, r->lrf_xqd, r->lv[lv].lambda, r->lrf_units, rect, r->lrf_fix_passes, r->stream);
 }
 
 // several tile groups (or a one-rank all-gather): each rank decides its own
@@ -2043,8 +2003,6 @@ void rv_replay_destroy(rv_replay *r) {
   // stream running)
   if (r->stream) (void)hipStreamSynchronize(r->stream);
   if (r->side) (void)hipStreamSynchronize(r->side);
-  if (r->rs2) (void)hipStreamSynchronize(r->rs2);
-  if (r->ecs) (void)hipStreamSynchronize(r->ecs);
   if (r->ech) {  // the host coder finishes the frames it holds, then stops
     {
       std::lock_guard<std::mutex> lk(r->ech->mu);
@@ -2060,11 +2018,7 @@ void rv_replay_destroy(rv_replay *r) {
     delete r->ech;
     r->ech = nullptr;
   }
-  if (r->ev_f8fork) (void)hipEventDestroy(r->ev_f8fork);
-  if (r->ev_f8done) (void)hipEventDestroy(r->ev_f8done);
-  if (r->ecs) (void)hipStreamDestroy(r->ecs);
-  for (hipStream_t es : r->edge)
-    if (es) (void)hipStreamSynchronize(es);
+  if (r->edge[1]) (void)hipStreamSynchronize(r->edge[1]);
   for (void *p : r->allocs) (void)hipFree(p);
   if (r->h_cnt) (void)hipHostFree(r->h_cnt);
   if (r->rr.h_pub) (void)hipHostFree(r->rr.h_pub);
@@ -2078,22 +2032,13 @@ void rv_replay_destroy(rv_replay *r) {
   if (r->ev_join) (void)hipEventDestroy(r->ev_join);
   if (r->ev_ielig) (void)hipEventDestroy(r->ev_ielig);
   if (r->side) (void)hipStreamDestroy(r->side);
-  if (r->rs2) (void)hipStreamDestroy(r->rs2);
-  for (hipEvent_t ev : {r->ev_rfork, r->ev_rlists, r->ev_rjoin})
-    if (ev) (void)hipEventDestroy(ev);
-  if (r->hp) (void)hipStreamSynchronize(r->hp), (void)hipStreamDestroy(r->hp);
-  if (r->lrf_side) (void)hipStreamSynchronize(r->lrf_side), (void)hipStreamDestroy(r->lrf_side);
-  for (hipEvent_t ev : {r->ev_lrf0, r->ev_lrf1})
-    if (ev) (void)hipEventDestroy(ev);
-  if (r->ev_hp0) (void)hipEventDestroy(r->ev_hp0);
-  if (r->ev_hp1) (void)hipEventDestroy(r->ev_hp1);
   for (hipEvent_t ev : {r->ev_efork, r->ev_l1me, r->ev_epart})
     if (ev) (void)hipEventDestroy(ev);
   for (int l = 0; l < kLevels; l++) {
     if (r->ev_ejoin[l]) (void)hipEventDestroy(r->ev_ejoin[l]);
     if (r->ev_ecommit[l]) (void)hipEventDestroy(r->ev_ecommit[l]);
-    if (r->edge[l] && (l <= 1 || r->edge[l] != r->edge[1])) (void)hipStreamDestroy(r->edge[l]);
   }
+  if (r->edge[1]) (void)hipStreamDestroy(r->edge[1]);  // (the other levels alias it)
   if (r->own_stream && r->stream) (void)hipStreamDestroy(r->stream);
   delete r;
 }
@@ -2192,8 +2137,6 @@ static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_r
     const size_t kb = ((size_t)g.nsb * (g.R * g.M + kCompModes)) * sizeof(CandKey);
     r->cand_key = (CandKey *)dalloc(r, kb);
     ok = ok && r->cand_key && hipMemsetAsync(r->cand_key, 0, kb, r->stream) == hipSuccess;
-    const char *e = getenv("RAV1E_HIP_F4_REUSE");  // =0: every round re-runs its F4 (A/B)
-    r->cand_reuse = !(e && e[0] == '0');
     r->f3dirty = (uint8_t *)dalloc(r, (size_t)g.nsb * g.R);
     r->f2dirty = (uint8_t *)dalloc(r, (size_t)g.nsb * g.R * 4);
     ok = ok && r->f3dirty && r->f2dirty;
@@ -2353,26 +2296,7 @@ static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_r
     }
     r->mv_active = (uint8_t *)dalloc(r, n);
     r->mv_list = (int32_t *)dalloc(r, 2 * n * 4);
-    r->mv_epoch = (uint32_t *)dalloc(r, n * 4);
-    ok = ok && r->stk && r->mv_active && r->mv_list && r->mv_epoch &&
-         hipMemsetAsync(r->mv_epoch, 0, n * 4, r->stream) == hipSuccess;
-    // RAV1E_HIP_MV_HP=1: the rounds after the first on a high-priority
-    // stream (2160p A/B: 140 vs 177 fps -- the other instance's work loses
-    // more than the rounds gain; off)
-    const char *hpe = getenv("RAV1E_HIP_MV_HP");
-    if (hpe && hpe[0] == '1') {
-      int least = 0, greatest = 0;
-      ok = ok && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
-           hipStreamCreateWithPriority(&r->hp, hipStreamNonBlocking, greatest) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_hp0, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_hp1, hipEventDisableTiming) == hipSuccess;
-    }
-    const char *rfe = getenv("RAV1E_HIP_ROUND_FORK");
-    if (rfe && rfe[0] == '1')
-      ok = ok && hipStreamCreateWithFlags(&r->rs2, hipStreamNonBlocking) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_rfork, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_rlists, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_rjoin, hipEventDisableTiming) == hipSuccess;
+    ok = ok && r->stk && r->mv_active && r->mv_list;
     // does a superblock's top-right neighbour (same tile) lie past the right
     // frame edge, i.e. is it a must_split leaf?
     for (int sb = 0; sb < g.nsb && r->lvl; sb++) {
@@ -2415,9 +2339,6 @@ static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_r
     r->lrf_xqd = (int8_t *)dalloc(r, (size_t)3 * lg.nsb * 32);
     r->lrf_units = (int8_t *)dalloc(r, (size_t)3 * lg.nsb * 3);
     ok = ok && r->lrf_err && r->lrf_xqd && r->lrf_units && alloc_input(r, r->lrf_out, false);
-    // RAV1E_LRF_SIDE=1: the decision on a side stream (2160p A/B, r05an:
-    // 136-142 vs 152-154 fps without -- one more stream per instance than
-    // the hardware queues serve well; off)
     // RAV1E_LRF_FIX=0 (A/B): the one-wave serial decision; RAV1E_LRF_FIX_PASSES
     // = 1 .. caps the fixed point's parallel passes (tests: the serial rest
     // after the cap).  Read here, once: the worker threads of a pipelined
@@ -2426,11 +2347,6 @@ static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_r
       const char *fe = getenv("RAV1E_LRF_FIX"), *fp = getenv("RAV1E_LRF_FIX_PASSES");
       r->lrf_fix_passes = (fe && fe[0] == '0') ? 0 : fp ? std::max(atoi(fp), 1) : 1 << 30;
     }
-    const char *se = getenv("RAV1E_LRF_SIDE");
-    if (se && se[0] == '1')
-      ok = ok && hipStreamCreateWithFlags(&r->lrf_side, hipStreamNonBlocking) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_lrf0, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_lrf1, hipEventDisableTiming) == hipSuccess;
   }
   r->entropy = (cfg->flags & RV_REPLAY_ENTROPY) != 0;
   if (r->entropy && g.xdec != g.ydec) {
@@ -2483,10 +2399,6 @@ static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_r
            hipEventCreateWithFlags(&eh->ev[k], hipEventBlockingSync | hipEventDisableTiming) ==
                hipSuccess;
     }
-    if (getenv("RAV1E_HIP_F8_STREAM") && atoi(getenv("RAV1E_HIP_F8_STREAM")))
-      ok = ok && hipStreamCreateWithFlags(&r->ecs, hipStreamNonBlocking) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_f8fork, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_f8done, hipEventDisableTiming) == hipSuccess;
     if (ok) eh->th = std::thread([eh] { eh->run(); });
   }
   r->imp_bx = g.vis_w / 8;
@@ -2515,16 +2427,11 @@ static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_r
     ok = ok && hipEventCreateWithFlags(&r->ev_efork, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&r->ev_l1me, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&r->ev_epart, hipEventDisableTiming) == hipSuccess;
-    // RAV1E_HIP_EDGE_STREAMS=3: one stream per level; default one stream for
-    // all levels (in order) -- every stream beyond the hardware queues
-    // (GPU_MAX_HW_QUEUES) is multiplexed onto them
-    const char *es = getenv("RAV1E_HIP_EDGE_STREAMS");
-    const bool per_level = es && es[0] == '3';
+    // one stream for all levels (in order): every stream beyond the hardware
+    // queues (GPU_MAX_HW_QUEUES) is multiplexed onto them
+    ok = ok && hipStreamCreateWithFlags(&r->edge[1], hipStreamNonBlocking) == hipSuccess;
     for (int l = 1; l < kLevels; l++) {
-      if (l == 1 || per_level)
-        ok = ok && hipStreamCreateWithFlags(&r->edge[l], hipStreamNonBlocking) == hipSuccess;
-      else
-        r->edge[l] = r->edge[1];  // an alias (destroyed once)
+      r->edge[l] = r->edge[1];
       ok = ok && hipEventCreateWithFlags(&r->ev_ejoin[l], hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&r->ev_ecommit[l], hipEventDisableTiming) == hipSuccess;
     }
@@ -2783,16 +2690,13 @@ template <typename Check, typename Eval>
 static int run_rounds(RoundRing &rr, hipStream_t xs, int budget, Check &&check, Eval &&eval,
                long *nrounds, long *nre, bool *changed, const char *what, long frame, int level) {
   static const bool mv_trace = getenv("RAV1E_HIP_MV_TRACE") != nullptr;
-  // RAV1E_HIP_ROUNDS_AHEAD=n: rounds queued beyond the last count read (A/B)
-  static const int ahead = getenv("RAV1E_HIP_ROUNDS_AHEAD") ? atoi(getenv("RAV1E_HIP_ROUNDS_AHEAD"))
-                                                            : rv_replay::kRoundsAhead;
   if (changed) *changed = false;
   rr.last_count = -1;
   const uint32_t first = rr.seq++;
   RV_R(check(first));
   int queued = 0;  // evaluation rounds queued (round j evaluates check j - 1's list)
   for (int seen = 0;; seen++) {
-    while (queued < budget && queued < seen + (ahead > 0 ? ahead : 1)) {
+    while (queued < budget && queued < seen + rv_replay::kRoundsAhead) {
       RV_R(eval(first + (uint32_t)queued));
       RV_R(check(rr.seq++));
       queued++;
@@ -3036,15 +2940,6 @@ static int la_step(rv_replay *r, long m) {
   RV_R(impwin_lists(e.f, lr.n, g.w_imp, g.h_imp, E.scratch, E.scratch_bytes, xs));
   const long last_frame = E.limit > 0 ? E.limit - 1 : -1;
   const size_t ni = (size_t)g.w_imp * g.h_imp;
-  // split: the passes run on lap once frame m's lists are in.  Entry reuse
-  // stays ordered: las waits ev_used of frame m - RW, recorded after that
-  // frame's encode waited its ev_imp on lap -- behind every earlier
-  // window's passes, the only other readers of the entry's lists.
-  if (E.split && E.imp_next <= m && (E.imp_next + E.W <= m || m == last_frame)) {
-    RV_H(hipEventRecord(e.ev_lists, xs));
-    RV_H(hipStreamWaitEvent(E.lap, e.ev_lists, 0));
-    xs = E.lap;
-  }
   while (E.imp_next <= m && (E.imp_next + E.W <= m || m == last_frame)) {
     const long n = E.imp_next, last = n + E.W < m ? n + E.W : m;
     {
@@ -3083,20 +2978,9 @@ static int la_step(rv_replay *r, long m) {
   return RV_OK;
 }
 
-// the engine's stream (RAV1E_HIP_LA_PRIORITY=1: the lowest priority, which
-// HIP serves from a queue pool of its own)
+// the engine's stream
 static int la_stream_create(RvLaEngine *E) {
-  const char *lpe = getenv("RAV1E_HIP_LA_PRIORITY");
-  const bool low = lpe && lpe[0] == '1';
-  int least = 0, greatest = 0;
-  if (low) {
-    RV_H(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    RV_H(hipStreamCreateWithPriority(&E->las, hipStreamNonBlocking, least));
-    if (E->split) RV_H(hipStreamCreateWithPriority(&E->lap, hipStreamNonBlocking, least));
-  } else {
-    RV_H(hipStreamCreateWithFlags(&E->las, hipStreamNonBlocking));
-    if (E->split) RV_H(hipStreamCreateWithFlags(&E->lap, hipStreamNonBlocking));
-  }
+  RV_H(hipStreamCreateWithFlags(&E->las, hipStreamNonBlocking));
   return RV_OK;
 }
 
@@ -3145,15 +3029,13 @@ static void la_engine_destroy(rv_replay *r) {
   }
   if (E->th.joinable()) E->th.join();
   if (E->las) (void)hipStreamSynchronize(E->las);
-  if (E->lap) (void)hipStreamSynchronize(E->lap);
   for (auto &en : E->ring)
-    for (hipEvent_t ev : {en.ev_imp, en.ev_used, en.ev_data, en.ev_xchg, en.ev_lists})
+    for (hipEvent_t ev : {en.ev_imp, en.ev_used, en.ev_data, en.ev_xchg})
       if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : E->hub_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (E->rr.h_pub) (void)hipHostFree(E->rr.h_pub);
   if (E->las) (void)hipStreamDestroy(E->las);
-  if (E->lap) (void)hipStreamDestroy(E->lap);
   delete E;  // its device arrays are the replay's allocations (freed with it)
 }
 
@@ -3296,28 +3178,12 @@ int rv_replay_set_imp_window(rv_replay *r, int window, long limit) {
   E->W = window;
   E->RW = window + 1 + RvLaEngine::kLaSlack;
   E->limit = limit;
-  // RAV1E_HIP_LA_PRIORITY=1: the engine's stream at the lowest priority.
-  // HIP keeps a queue pool per priority, so it then gets a hardware queue of
-  // its own instead of sharing one (GPU_MAX_HW_QUEUES: 4) with the twin's
-  // stream.  Measured at 2160p (r04p1): 101-103 vs 118 fps -- the lookahead's
-  // kernels then run beside the rounds' and slow them more than the shared
-  // queue's ordering does; off.
-  //
-  // The stream is created on the engine's thread when the first frame is
+  // The engine's stream is created on its thread when the first frame is
   // asked for, after the twin instance's streams: HIP gives a new stream the
   // least-used hardware queue, so the engine's then shares one with a
   // frame-edge or entropy stream instead of with the twin's round kernels
   // (which the trace showed waiting 6-7 us behind the lookahead's).
-  // RAV1E_HIP_LA_LAZY=0: created here (A/B).
-  // RAV1E_HIP_LA_SPLIT=1: the window passes on a stream of their own.  Off:
-  // the extra stream shares the 4 hardware queues with the encode's and
-  // measured 4-10 % slower (profiles/r05i_*).
-  const char *spe = getenv("RAV1E_HIP_LA_SPLIT");
-  E->split = spe && spe[0] == '1';
-  const char *lze = getenv("RAV1E_HIP_LA_LAZY");
-  const bool lazy = !(lze && lze[0] == '0');
-  bool ok = hipGetDevice(&E->dev) == hipSuccess &&
-            (lazy || la_stream_create(E) == RV_OK) && round_ring_alloc(r, E->rr, r->stream);
+  bool ok = hipGetDevice(&E->dev) == hipSuccess && round_ring_alloc(r, E->rr, r->stream);
   const int ni = g.w_imp * g.h_imp, nr = g.nsb * r->RA;  // the lookahead's references
   E->la_list = ok ? (int32_t *)dalloc(r, (size_t)nr * 20 * 4) : nullptr;
   E->scratch_bytes = impwin_scratch_bytes(ni);
@@ -3332,8 +3198,7 @@ int rv_replay_set_imp_window(rv_replay *r, int window, long limit) {
          hipEventCreateWithFlags(&en.ev_imp, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&en.ev_used, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&en.ev_data, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&en.ev_xchg, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&en.ev_lists, hipEventDisableTiming) == hipSuccess;
+         hipEventCreateWithFlags(&en.ev_xchg, hipEventDisableTiming) == hipSuccess;
     if (!ok) break;
     en.o.coarse = (rv_fs_result *)m;
     en.o.half_l = en.o.coarse + nr;
@@ -3879,17 +3744,13 @@ int rv_replay_frame(rv_replay *r, rv_replay_frame_info *info) {
     ma.hq = r->half_l;
     ma.prev = r->slots[fi.ref_display[0] % kSlots].fmv;  // the LAST reference's frame_mvs
     ma.edge_ok = 0;
-    ma.f3dirty = r->cand_reuse ? r->f3dirty : nullptr;
-    static const bool gla = getenv("RAV1E_HIP_GUESS_LA") && getenv("RAV1E_HIP_GUESS_LA")[0] == '1';
-    ma.field_guess_la = gla ? 1 : 0;
-    static const bool f2d = !(getenv("RAV1E_HIP_F2_DIRTY") && getenv("RAV1E_HIP_F2_DIRTY")[0] == '0');
-    ma.f2dirty = r->cand_reuse && f2d ? r->f2dirty : nullptr;
+    ma.f3dirty = r->f3dirty;
+    ma.f2dirty = r->f2dirty;
     // the first check marks every superblock (its count is not read)
     const uint32_t q = r->rr.seq++;
     ma.count = slot_cnt(q);
     ma.pub = r->rr.pub(q);
     ma.list = mvl(q);
-    ma.plist = nullptr;
     RV_R(rv_mvref_round(ma, st));
   }
   // F2: build_half_res_pmvs of the encode (speed 10: the sets the check
@@ -3917,9 +3778,7 @@ int rv_replay_frame(rv_replay *r, rv_replay_frame_info *info) {
   lc4.n_tx = g.nsb * cg.comp;
   cc4.n_tx = g.nsb * cg.comp * ntx_c;
   const RdoArgs f4h[4] = {la4, ca4, lc4, cc4};
-  // RAV1E_HIP_F4_LIST=0: the full-grid launches (A/B); 12-bit keeps them
-  static const bool f4_list_env = !(getenv("RAV1E_HIP_F4_LIST") && getenv("RAV1E_HIP_F4_LIST")[0] == '0');
-  const bool f4_list = f4_list_env && g.bd != 12;
+  const bool f4_list = g.bd != 12;  // 12-bit keeps the full-grid launches
   if (f4_list) RV_R(rv_rdo_args_put(f4h, cg.comp ? 4 : 2, r->f4_args, st));
   // F3 full-res full-pel diamond -> sub-pel predictor; sub-pel diamond
   // (speed 10: SAD, no hp) -> NEWMV of every superblock and reference;
@@ -3981,14 +3840,6 @@ int rv_replay_frame(rv_replay *r, rv_replay_frame_info *info) {
   // the first round of a run lists most superblocks (check 1 after round 0:
   // 70-80 % at 2160p): its searches take full grids, later ones the pool
   uint32_t q_first = 0;
-  // RAV1E_HIP_F4_PAIR=0: the rounds' single and compound F4 in two launches (A/B)
-  static const bool f4_pair = !(getenv("RAV1E_HIP_F4_PAIR") && getenv("RAV1E_HIP_F4_PAIR")[0] == '0');
-  // RAV1E_HIP_F2_F3=0: the rounds' F2 and F3 full-pel searches in two launches (A/B)
-  static const bool f2_f3 = !(getenv("RAV1E_HIP_F2_F3") && getenv("RAV1E_HIP_F2_F3")[0] == '0');
-  // RAV1E_HIP_F3_FUSE=0: the rounds' F3 sub-pel searches in a launch of their
-  // own after F2 || F3 full-pel (A/B); fused, each F3 workgroup runs its
-  // job's sub-pel search right after the full-pel one
-  static const bool f3_fuse = !(getenv("RAV1E_HIP_F3_FUSE") && getenv("RAV1E_HIP_F3_FUSE")[0] == '0');
   auto f3_f4_list = [&](hipStream_t xs, uint32_t q) -> int {
     const int32_t *acnt = slot_cnt(q);
     int lg = q == q_first ? nr * g.R : 0;
@@ -3997,89 +3848,42 @@ int rv_replay_frame(rv_replay *r, rv_replay_frame_info *info) {
     // carry the live work and few empty workgroups (a round's fixed pools
     // put ~12 k waves through the dispatcher for a few dozen superblocks).
     // A list longer than the hint loops over the grid, so the hint only
-    // sizes, never decides.  RAV1E_HIP_ROUND_HINT=0: the fixed pools (A/B).
-    static const bool round_hint = !(getenv("RAV1E_HIP_ROUND_HINT") && getenv("RAV1E_HIP_ROUND_HINT")[0] == '0');
-    const int hint = q == q_first || !round_hint ? -1 : r->rr.last_count;
+    // sizes, never decides.
+    const int hint = q == q_first ? -1 : r->rr.last_count;
     const int hsb = hint >= 0 ? std::max(2 * hint, 16) : 0;
     int f4_grid = 0;
     if (hsb) {
       lg = std::min(hsb * g.R, 512);
       f4_grid = std::min(6 * hsb, 1024);
     }
-    // the check's F2 / F3 sets came from the state before this round, so F2
-    // and F3 are independent (F2's results feed the next check): F2 on the
-    // second stream
-    hipStream_t x2 = r->rs2 ? r->rs2 : xs;
-    if (r->rs2) {
-      RV_H(hipEventRecord(r->ev_rfork, xs));
-      RV_H(hipStreamWaitEvent(x2, r->ev_rfork, 0));
-    }
-    const bool fused = f2_f3 && f3_fuse && !r->rs2 && !r->s6;
-    if (f2_f3 && !r->rs2) {  // F2 and F3 full-pel (+ F3 sub-pel when fused) in one launch
-      // fused: the probe brackets the launch (its sub-pel candidates, its span)
-      if (fused) RV_R(kp_open(xs));
-      RV_R(rv_diamond_f2_f3(&cur.hres, refs_h, r->jobs_half[lv], r->half, ma.f2dirty, &cur.y,
-                            refs_y, r->jobs_full[lv], r->full, ma.f3dirty, &to_sub, g.R, nr, g.bd,
-                            mvl(q), acnt, lg, xs, fused ? r->jobs_sub[lv] : nullptr,
-                            fused ? r->sub : nullptr, fused ? kp_acc : nullptr,
-                            fused ? kp_ts() : nullptr));
-      if (fused) RV_R(kp_close(xs));
-    } else {
-      // F2 of the listed superblocks (their 4 quadrants per reference)
-      RV_R(rv_diamond_search_multi(&cur.hres, refs_h, g.R, r->jobs_half[lv], nr * 4, 16, 16, 0, 0,
-                                   0, g.bd, r->half, nullptr, nullptr, x2, nullptr, mvl(q),
-                                   acnt, 4, ma.f2dirty, lg));
-      // F3 of the listed superblocks: only the jobs whose set or pmv changed
-      RV_R(rv_diamond_search_multi(&cur.y, refs_y, g.R, r->jobs_full[lv], nr, 64, 64, 0, 0, 0,
-                                   g.bd, r->full, nullptr, &to_sub, xs, nullptr, mvl(q), acnt,
-                                   1, ma.f3dirty, lg));
-    }
-    if (!fused) {
-      RV_R(kp_open(xs));
-      RV_R(rv_diamond_search_multi(&cur.y, refs_y, g.R, r->jobs_sub[lv], nr, 64, 64, 1, 0, 0, g.bd,
-                                   r->sub, nullptr, nullptr, xs, nullptr, mvl(q), acnt, 1,
-                                   ma.f3dirty, lg, kp_acc, kp_ts()));
-      RV_R(kp_close(xs));
-    }
-    // the pools of the small per-round kernels: kRoundGrid for a run's first
-    // round (most superblocks listed), RAV1E_HIP_ROUND_POOL (A/B) after it
-    static const int round_pool = getenv("RAV1E_HIP_ROUND_POOL") ? std::max(1, atoi(getenv("RAV1E_HIP_ROUND_POOL")))
-                                                                 : kRoundGrid;
-    const int rg = q == q_first ? kRoundGrid
-                   : hsb ? std::min(kRoundGrid, std::max((14 * hsb + 255) / 256, (hsb + 3) / 4))
-                         : round_pool;
+    // F2 and F3 full-pel of the listed superblocks in one launch (the check's
+    // sets came from the state before this round, so they are independent;
+    // only the jobs whose set or pmv changed run), with F3's sub-pel search
+    // fused into it: each F3 workgroup runs its job's sub-pel search right
+    // after the full-pel one.  The probe brackets the launch (its sub-pel
+    // candidates, its span).  (The rounds are speed 10's: SAD, no half-pel.)
+    RV_R(kp_open(xs));
+    RV_R(rv_diamond_f2_f3(&cur.hres, refs_h, r->jobs_half[lv], r->half, ma.f2dirty, &cur.y,
+                          refs_y, r->jobs_full[lv], r->full, ma.f3dirty, &to_sub, g.R, nr, g.bd,
+                          mvl(q), acnt, lg, xs, r->jobs_sub[lv], r->sub, kp_acc, kp_ts()));
+    RV_R(kp_close(xs));
+    // the pools of the small per-round kernels: kRoundGrid unless the hint sizes them
+    const int rg = hsb ? std::min(kRoundGrid, std::max((14 * hsb + 255) / 256, (hsb + 3) / 4))
+                       : kRoundGrid;
     round_lists_kernel<<<rg, 256, 0, xs>>>(
         cg, r->sub, nsingle, r->cand_list, r->cand_count, mvl(q), acnt,
-        CandKeys{r->cand_key, (uint32_t)(r->coded + 1), r->cand_reuse ? 1 : 0});
-    if (r->rs2) {  // the lists are out: the compound F4 runs beside the single one
-      RV_H(hipEventRecord(r->ev_rlists, xs));
-      RV_H(hipStreamWaitEvent(x2, r->ev_rlists, 0));
-    }
-    // F4: a pool of workgroups over the live list entries (rdo_quad_list_kernel;
-    // RAV1E_HIP_F4_LIST=0: full grids whose workgroups past the device counts
-    // exit at once); on a compound frame the single and compound candidates
-    // in one launch
-    if (cg.comp) {
-      if (f4_list && f4_pair && !r->rs2) {  // the pool over both lists
-        RV_R(kp_open(xs, 1));
-        RV_R(rv_rdo_candidates_list(f4h, r->f4_args, 2, 0, g.hbd, xs, f4_grid, kp_f4, kp_ts(1)));
-        RV_R(kp_close(xs, 1));
-      } else if (f4_pair && !r->rs2) {
-        RV_R(rv_rdo_candidates_pair(la4, ca4, lc4, cc4, g.hbd, xs));
-      } else {
-        RV_R(rv_rdo_candidates(la4, ca4, g.hbd, xs));
-        RV_R(rv_rdo_candidates(lc4, cc4, g.hbd, x2, true));
-      }
-    } else if (f4_list) {
+        CandKeys{r->cand_key, (uint32_t)(r->coded + 1), 1});
+    // F4: a pool of workgroups over the live list entries (rdo_quad_list_kernel),
+    // on a compound frame the single and compound candidates in one launch;
+    // 12-bit: full grids whose workgroups past the device counts exit at once
+    if (f4_list) {
       RV_R(kp_open(xs, 1));
-      RV_R(rv_rdo_candidates_list(f4h, r->f4_args, 1, 0, g.hbd, xs, f4_grid, kp_f4, kp_ts(1)));
+      RV_R(rv_rdo_candidates_list(f4h, r->f4_args, cg.comp ? 2 : 1, 0, g.hbd, xs, f4_grid, kp_f4,
+                                  kp_ts(1)));
       RV_R(kp_close(xs, 1));
     } else {
       RV_R(rv_rdo_candidates(la4, ca4, g.hbd, xs));
-    }
-    if (r->rs2) {  // F2 and the compound F4 join before the argmin
-      RV_H(hipEventRecord(r->ev_rjoin, x2));
-      RV_H(hipStreamWaitEvent(xs, r->ev_rjoin, 0));
+      if (cg.comp) RV_R(rv_rdo_candidates(lc4, cc4, g.hbd, xs, true));
     }
     score_wave_kernel<<<rg, 256, 0, xs>>>(
         g, cg, L.lambda, L.ds[1], L.ds[2], r->sub, r->l_out, r->c_out, r->c_out + nct * 3, ntx_c,
@@ -4107,62 +3911,18 @@ int rv_replay_frame(rv_replay *r, rv_replay_frame_info *info) {
   int mv_runs = 0;
   auto mv_rounds_run = [&](const uint8_t *iwas, bool *changed) -> int {
     mv_runs++;
-    hipStream_t xs = r->hp ? r->hp : st;
-    // the rounds follow the main stream's work and it waits for them
-    struct Join {
-      rv_replay *r;
-      hipStream_t st;
-      ~Join() {
-        if (r->hp && hipEventRecord(r->ev_hp1, r->hp) == hipSuccess)
-          (void)hipStreamWaitEvent(st, r->ev_hp1, 0);
-      }
-    } join{r, st};
-    if (r->hp) {
-      RV_H(hipEventRecord(r->ev_hp0, st));
-      RV_H(hipStreamWaitEvent(r->hp, r->ev_hp0, 0));
-    }
     q_first = r->rr.seq;  // run_rounds' first check (its list: the first round)
-    // Long chains (a change running down a tile's columns, one superblock
-    // row per Jacobi round: compound frames reach ~70 rounds at 2160p): from
-    // check kScanAfter on, up to kScanMax checks are the predictive scan
-    // (mvref_scan_kernel), which lets a chain run down in one round when the
-    // predicted decisions hold.  The Jacobi bound still holds after them, so
-    // the run's budget grows by kScanMax.
-    static const int scan_after = getenv("RAV1E_HIP_MV_SCAN_AFTER")
-                                      ? atoi(getenv("RAV1E_HIP_MV_SCAN_AFTER")) : 0;
-    constexpr int kScanMax = 8;
-    const bool scans = scan_after > 0;
     return rounds(
-        xs, budget + (scans ? kScanMax : 0),
+        st, budget,
         [&](uint32_t q) {
           ma.init = 0;
           ma.iwas = iwas;
           ma.count = slot_cnt(q);
           ma.pub = r->rr.pub(q);
           ma.list = mvl(q);
-          // RAV1E_HIP_CHECK_INC=1 (A/B, off: DESIGN.md §8): from the run's
-          // third check on, each check covers only the dependents of the
-          // previous check's list.  The second check follows the run's
-          // first round, which lists most superblocks: it stays full (their
-          // dependents, 4 per listed superblock, would take the incremental
-          // kernel several passes).  The incremental grid is the full
-          // check's: a short list leaves most workgroups empty, which exit
-          // at once, and a long one never loops.
-          static const bool inc = getenv("RAV1E_HIP_CHECK_INC") && getenv("RAV1E_HIP_CHECK_INC")[0] == '1';
-          if (inc && q > q_first + 1) {
-            ma.plist = mvl(q - 1);
-            ma.pcount = slot_cnt(q - 1);
-            ma.epoch = r->mv_epoch;
-            ma.tag = q + 1;
-            ma.inc_grid = 0;
-          } else {
-            ma.plist = nullptr;
-          }
-          const uint32_t c = q - q_first;
-          return rv_mvref_round(ma, xs, scans && c >= (uint32_t)scan_after &&
-                                            c < (uint32_t)(scan_after + kScanMax));
+          return rv_mvref_round(ma, st);
         },
-        [&](uint32_t q) { return f3_f4_list(xs, q); }, &r->mv_round_sum, &r->mv_reeval, changed,
+        [&](uint32_t q) { return f3_f4_list(st, q); }, &r->mv_round_sum, &r->mv_reeval, changed,
         "mvref");
   };
   if (r->exact) {
@@ -4205,11 +3965,6 @@ int rv_replay_frame(rv_replay *r, rv_replay_frame_info *info) {
   }
   if (r->intra) RV_R(intra_begin(r));
   RV_EV(9);
-  // the previous frame's F8 still reads the committed levels and the block map
-  if (r->f8_pending) {
-    RV_H(hipStreamWaitEvent(st, r->ev_f8done, 0));
-    r->f8_pending = false;
-  }
   // F6 commit the winners into the frame: the levels' leaves (speed 10: on
   // the edge stream, beside the superblocks' commit)
   if (edge) {
@@ -4343,21 +4098,10 @@ int rv_replay_frame(rv_replay *r, rv_replay_frame_info *info) {
     EcFrameBufs b = r->ecb;
     RV_H(hipHostGetDevicePointer((void **)&b.tokens, eh->tok_h[slot], 0));
     RV_H(hipHostGetDevicePointer((void **)&b.stat, eh->stat_h[slot], 0));
-    // RAV1E_HIP_F8_STREAM=1: on its own stream (A/B; default: the main one)
-    const bool own = r->ecs != nullptr;
-    hipStream_t es = own ? r->ecs : st;
-    if (own) {
-      RV_H(hipEventRecord(r->ev_f8fork, st));
-      RV_H(hipStreamWaitEvent(r->ecs, r->ev_f8fork, 0));
-    }
-    if (tm) RV_H(hipEventRecord(e[rv_replay::kStageEv + 4], es));
-    RV_R(ec_frame_tokens(ea, b, es));
-    if (tm) RV_H(hipEventRecord(e[rv_replay::kStageEv + 5], es));
-    RV_H(hipEventRecord(eh->ev[slot], es));
-    if (own) {
-      RV_H(hipEventRecord(r->ev_f8done, r->ecs));
-      r->f8_pending = true;
-    }
+    if (tm) RV_H(hipEventRecord(e[rv_replay::kStageEv + 4], st));
+    RV_R(ec_frame_tokens(ea, b, st));
+    if (tm) RV_H(hipEventRecord(e[rv_replay::kStageEv + 5], st));
+    RV_H(hipEventRecord(eh->ev[slot], st));
     const int q = r->lv[lv].qidx;
     {
       std::lock_guard<std::mutex> lk(eh->mu);

@@ -538,9 +538,22 @@ def _gpu_vs_cpu(w, h, xdec, ydec, bd, refs, frames, tiling=None, flags=0, imp=No
     (384, 192, 1, 1, 8, 2, {"tile_cols": 2}, _LRF),
     (192, 128, 1, 1, 12, 1, None, _LRF),
     (256, 200, 1, 1, 8, 2, None, _LRF | RP.RV_REPLAY_SPEED6),
+    # 12 bits, compound: the rounds' full-grid F4, single then compound candidates
+    # (last in the list: the ids of the cases above carry their position)
+    (192, 128, 1, 1, 12, 2, None, RP.RV_REPLAY_DEBLOCK | RP.RV_REPLAY_CDEF),
 ])
 def test_gpu_replay_matches_cpu_replay(w, h, xdec, ydec, bd, refs, tiling, flags):
     _gpu_vs_cpu(w, h, xdec, ydec, bd, refs, 10, tiling, flags)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", [_LRF, _LRF | RP.RV_REPLAY_SPEED6])
+def test_gpu_replay_serial_mode(monkeypatch, flags):
+    """RAV1E_HIP_REPLAY_SERIAL=1 (the profiling mode, read at create): the
+    lookahead and the frame-edge levels on the replay's one stream. Every
+    word equals the CPU replay's."""
+    monkeypatch.setenv("RAV1E_HIP_REPLAY_SERIAL", "1")
+    _gpu_vs_cpu(256, 200, 1, 1, 8, 2, 10, None, flags)
 
 
 @pytest.mark.gpu
