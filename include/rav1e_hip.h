@@ -624,6 +624,100 @@ long rv_ec_count_stream(const uint32_t *tokens, size_t n, uint16_t *cdf_all, uin
 int rv_ec_cdf_total_all(void);
 int rv_ec_default_cdf_all(int qctx, uint16_t *out);
 void rv_ec_reset_counts_all(uint16_t *cdf);
+/* partition_gather_vert_alike (gather 1) / _horz_alike (gather 2)
+ * (src/context.rs:1995-2057) of one 10-type partition CDF (cdf[0..10), host):
+ * the first entry x of the 2-entry CDF [x, 0] the edge token is coded
+ * against.  The function rv_ec_code_stream, rv_ec_count_stream and
+ * rv_ec_rate_stream_batch share.  RV_EINVAL for another gather. */
+int rv_ec_partition_gather(const uint16_t *cdf, int gather);
+
+/* ---- whole RDO candidates (src/rdo.rs:689-768) ---------------------------
+ * luma_chroma_mode_rdo prices a candidate by writing write_partition
+ * (bsize >= BLOCK_8X8 && is_sqr), encode_block_pre_cdef and
+ * encode_block_post_cdef (mode info, then the transform tree's coefficients)
+ * into one WriterCounter whose CDFs adapt, and taking the tell_frac()
+ * difference.
+ *
+ * rv_ec_rate_stream_batch: rv_ec_rate_batch over the combined table and mixed
+ * streams.  Same arguments, groups, d_init, d_rate and d_status, with these
+ * differences: d_cdfs_all holds n_cdfs snapshots of rv_ec_cdf_total_all() u16
+ * each (read only, 2-byte aligned); a token is a symbol of either part of the
+ * table (a sliced CDF carries the slice's length, the counter in its last
+ * entry), a raw bit, or the frame-edge partition token (bits 23-24 the
+ * gather, bits 25-26 bsl), which is coded against the 2-entry CDF gathered
+ * from the group's adapting partition CDF and adapts nothing.  Bad, beside
+ * rv_ec_code_stream's token test against the combined total: an edge token
+ * with gather 3, with a CDF that is not one whole partition CDF, or with a
+ * symbol above 1 (gather 0 is an ordinary symbol).  A coefficient-only stream
+ * rates what rv_ec_rate_batch rates from the snapshots' first
+ * rv_ec_cdf_total() entries.
+ * rv_ec_rate_stream_batch_waves: the same with `waves` (1, 2 or 4) groups per
+ * workgroup, for measuring; rv_ec_rate_stream_batch uses 4. */
+int rv_ec_rate_stream_batch(const uint32_t *d_tokens, const uint32_t *d_offsets,
+                            const int32_t *d_group_first, int n_groups,
+                            const uint16_t *d_cdfs_all, int n_cdfs, const int32_t *d_group_cdf,
+                            const uint32_t *d_init, uint32_t *d_rate, uint32_t *d_status,
+                            void *stream);
+int rv_ec_rate_stream_batch_waves(const uint32_t *d_tokens, const uint32_t *d_offsets,
+                                  const int32_t *d_group_first, int n_groups,
+                                  const uint16_t *d_cdfs_all, int n_cdfs,
+                                  const int32_t *d_group_cdf, const uint32_t *d_init,
+                                  uint32_t *d_rate, uint32_t *d_status, int waves, void *stream);
+/* rv_ec_cand: one candidate.  block: the index of its block (rv_ec_mode_job
+ * kind 0) in d_mode_jobs; part: the index of its partition node (kind 1, at
+ * the block's tile, position and size) or -1; its transform blocks are
+ * d_tx_jobs[tx_first .. tx_first + tx_count) (rv_ec_job kind 0, `tile` the
+ * block's, top-left inside the block, luma then chroma in write_tx_tree /
+ * write_tx_blocks' order; none for a skip block).  The candidates'
+ * transform-block ranges do not overlap. */
+typedef struct rv_ec_cand {
+  int32_t part, block, tx_first, tx_count;
+} rv_ec_cand;
+/* rv_ec_cand_tokenize: every candidate's tokens against a frozen coding
+ * state.  d_coef_map (n_tiles * 3 * map_w4 * map_h4 bytes, with xdec / ydec)
+ * is what rv_ec_tokenize left in its d_map after the committed jobs,
+ * d_mode_map (n_tiles * map_w8 * map_h8 u32, with d_tile_dims and params)
+ * what rv_ec_mode_tokenize left in its d_map; neither is written.  Candidate
+ * c's tokens are d_tokens[d_offsets[c] .. d_offsets[c + 1]): partition,
+ * encode_block_pre_cdef, the mode symbols of encode_block_post_cdef, then its
+ * transform blocks' coefficient tokens.  They equal the tokens the block
+ * would get appended to the committed job lists and tokenized by those two
+ * entry points; maps built from more blocks than those coded before the
+ * candidate (the whole frame's) give the same tokens, because a block reads
+ * only cells above and left of it.  Candidates are independent of each
+ * other; a candidate's transform blocks read the contexts its earlier ones
+ * set.  d_scratch: rv_ec_cand_scratch_bytes(n, n_tx_jobs) bytes, 16-byte
+ * aligned.  d_status 3 u32 (cleared here): [0] total tokens, [1] 1 if the
+ * total exceeded token_cap (tokens past it were dropped), [2] the rejected
+ * candidates: outside rv_ec_mode_tokenize's restrictions, or with an index,
+ * a partition node or a transform block that does not fit the block or the
+ * maps; they emit nothing and nothing of them is used as an index.  Returns 0
+ * or an error (n <= 2^20, n_tx_jobs <= 2^24, n_tiles <= 1024). */
+size_t rv_ec_cand_scratch_bytes(int n_cands, int n_tx_jobs);
+int rv_ec_cand_tokenize(const rv_ec_cand *d_cands, int n, const rv_ec_mode_job *d_mode_jobs,
+                        int n_mode_jobs, const rv_ec_job *d_tx_jobs, int n_tx_jobs,
+                        rv_ec_mode_params params, int n_tiles, const int32_t *d_tile_dims, int xdec,
+                        int ydec, int map_w4, int map_h4, const uint8_t *d_coef_map, int map_w8,
+                        int map_h8, const uint32_t *d_mode_map, void *d_scratch,
+                        uint32_t *d_offsets, uint32_t *d_tokens, uint32_t token_cap,
+                        uint32_t *d_status, void *stream);
+/* rv_ec_cand_rates: rv_ec_cand_tokenize, then rv_ec_rate_stream_batch with
+ * one group per candidate, on one stream without a host synchronisation
+ * between them: d_rate[c] is what wr.tell_frac() - tell is in
+ * luma_chroma_mode_rdo for candidate c priced from snapshot d_group_cdf[c]
+ * (NULL: snapshot 0) and writer state d_init[c] (NULL: fresh).  The tokens
+ * and offsets stay in the caller's buffers; after an overflow (d_status[1])
+ * the offsets are cut down to token_cap and the rates of the cut candidates
+ * mean nothing.  d_status 4 u32: [0..2] as above, [3] the counter's bad
+ * groups (rate 0xFFFFFFFF).  A rejected candidate has no tokens and rates 0. */
+int rv_ec_cand_rates(const rv_ec_cand *d_cands, int n, const rv_ec_mode_job *d_mode_jobs,
+                     int n_mode_jobs, const rv_ec_job *d_tx_jobs, int n_tx_jobs,
+                     rv_ec_mode_params params, int n_tiles, const int32_t *d_tile_dims, int xdec,
+                     int ydec, int map_w4, int map_h4, const uint8_t *d_coef_map, int map_w8,
+                     int map_h8, const uint32_t *d_mode_map, void *d_scratch, uint32_t *d_offsets,
+                     uint32_t *d_tokens, uint32_t token_cap, const uint16_t *d_cdfs_all, int n_cdfs,
+                     const int32_t *d_group_cdf, const uint32_t *d_init, uint32_t *d_rate,
+                     uint32_t *d_status, void *stream);
 
 /* dc_q / ac_q lookups (src/quantize.rs:42-62) on the host: ac = 0 for
  * dc_qlookup*_Q3, 1 for ac_qlookup*_Q3; -1 on bad arguments. */

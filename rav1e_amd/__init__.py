@@ -354,6 +354,15 @@ def _declare(L):
         "rv_ec_cdf_total_all": (i32, []),
         "rv_ec_default_cdf_all": (i32, [i32, vp]),
         "rv_ec_reset_counts_all": (None, [vp]),
+        "rv_ec_partition_gather": (i32, [vp, i32]),
+        "rv_ec_rate_stream_batch": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+        "rv_ec_rate_stream_batch_waves": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp]),
+        "rv_ec_cand_scratch_bytes": (C.c_size_t, [i32, i32]),
+        "rv_ec_cand_tokenize": (i32, [vp, i32, vp, i32, vp, i32, RvEcModeParams, i32, vp, i32, i32,
+                                      i32, i32, vp, i32, i32, vp, vp, vp, vp, C.c_uint32, vp, vp]),
+        "rv_ec_cand_rates": (i32, [vp, i32, vp, i32, vp, i32, RvEcModeParams, i32, vp, i32, i32,
+                                   i32, i32, vp, i32, i32, vp, vp, vp, vp, C.c_uint32, vp, i32, vp,
+                                   vp, vp, vp, vp]),
         "rv_sad_fn": (vp, [i32, i32, i32]),
         "rv_satd_fn": (vp, [i32, i32, i32]),
         "rv_put_fn_get": (vp, [i32, i32, i32]),
@@ -1382,8 +1391,8 @@ class _EcTokens:
     """rv_ec_tokenize of a coding-order job list: the device buffers and the
     tile starts."""
 
-    def __init__(self, jobs, coeffs, xdec, ydec, what):
-        jobs = np.asarray(jobs, np.int64)
+    def __init__(self, jobs, coeffs, xdec, ydec, what, min_tiles=1, min_map=(1, 1)):
+        jobs = np.asarray(jobs, np.int64).reshape(-1, 10)
         n = len(jobs)
         self.n = n
         self.co = DeviceBuffer.from_array(np.ascontiguousarray(coeffs, np.int32))
@@ -1397,18 +1406,20 @@ class _EcTokens:
         tile = np.cumsum(jobs[:, 0] == 3) - 1
         ej["tile"] = np.maximum(tile, 0)
         ej["coeffs"] = self.co.ptr + 4 * jobs[:, 9].astype(np.uint64)
-        self.starts, self.ntiles = starts, len(starts)
+        self.starts, self.ntiles = starts, max(len(starts), int(min_tiles))
         ext = np.where(jobs[:, 0] == 0, 1 << jobs[:, 4], np.where(jobs[:, 0] == 1, 1 << np.maximum(jobs[:, 7] - 2, 0), 0))
-        mw = int(max(1, (jobs[:, 2] + ext).max()))
-        mh = int(max(1, (jobs[:, 3] + ext).max()))
-        dj = DeviceBuffer.from_array(ej)
+        mw = int(max(min_map[0], (jobs[:, 2] + ext).max() if n else 1))
+        mh = int(max(min_map[1], (jobs[:, 3] + ext).max() if n else 1))
+        dj = DeviceBuffer.from_array(ej) if n else None
         dmap = DeviceBuffer(self.ntiles * 3 * mw * mh)
+        self.dmap, self.mw, self.mh = dmap, mw, mh  # the context map the jobs leave behind
         scr = DeviceBuffer(lib().rv_ec_scratch_bytes(n))
         self.doff = DeviceBuffer(4 * (n + 1))
         cap = int(64 * n + 8 * int(np.asarray(coeffs).size) + 1024)
         self.dtok = DeviceBuffer(4 * cap)
         dst = DeviceBuffer(8)
-        _check(lib().rv_ec_tokenize(dj.ptr, n, xdec, ydec, self.ntiles, mw, mh, dmap.ptr, scr.ptr,
+        _check(lib().rv_ec_tokenize(dj.ptr if n else None, n, xdec, ydec, self.ntiles, mw, mh,
+                                    dmap.ptr, scr.ptr,
                                     self.doff.ptr, self.dtok.ptr, cap, dst.ptr, None),
                "rv_ec_tokenize")
         _sync(None)
@@ -1608,6 +1619,12 @@ def ec_tokenize_modes(jobs, params, stack_mvs=None, check=True):
     jobs = np.ascontiguousarray(jobs, EC_MODE_JOB)
     if check:
         check_mode_jobs(jobs, stack_mvs)
+    return _ec_mode_tokenize(jobs, params)[:3]
+
+
+def _ec_mode_tokenize(jobs, params):
+    """rv_ec_mode_tokenize: (tokens, offsets, rejected, the neighbour-record map
+    the jobs leave behind (device), its (w8, h8), the tile sizes (device))."""
     n = len(jobs)
     dims = params.tile_dims
     nt = len(dims)
@@ -1629,7 +1646,7 @@ def ec_tokenize_modes(jobs, params, stack_mvs=None, check=True):
     if status[1]:
         raise Rav1eHipError("ec_tokenize_modes: token buffer overflow")
     return (dtok.download(np.uint32)[:int(status[0])], doff.download(np.uint32)[:n + 1],
-            int(status[2]))
+            int(status[2]), dmap, (mw, mh), ddim)
 
 
 def code_tile(mode_jobs, coeff_jobs, coeffs, coeff_after, params, cdf_init, xdec=1, ydec=1,
@@ -1718,6 +1735,246 @@ def coefficient_rates(jobs, coeffs, group_first, cdfs, xdec, ydec, group_cdf=Non
     if bad:
         raise Rav1eHipError(f"coefficient_rates: {bad} groups with a bad token or snapshot index")
     return rates, tk.tokens(), tk.offsets()
+
+
+# ---- whole RDO candidates (rv_ec_rate.hip's stream kernel, rv_ec_cand.hip) ---
+EC_CAND = np.dtype([("part", "<i4"), ("block", "<i4"), ("tx_first", "<i4"), ("tx_count", "<i4")])
+_BSIZE_N4 = {3: 2, 6: 4, 9: 8, 12: 16}  # BLOCK_8X8 .. BLOCK_64X64 in luma 4x4 units
+
+
+def ec_partition_gather(cdf, gather):
+    """partition_gather_vert_alike (1) / _horz_alike (2) of one partition CDF
+    (>= 10 u16): the x of the 2-entry CDF [x, 0], by the function the host
+    coders and the device counter share."""
+    cdf = np.ascontiguousarray(cdf, np.uint16)
+    if cdf.size < 10:
+        raise Rav1eHipError("ec_partition_gather: a partition CDF has 10 entries and a counter")
+    x = lib().rv_ec_partition_gather(cdf.ctypes.data, int(gather))
+    if x < 0:
+        _check(int(x), "rv_ec_partition_gather")
+    return int(x)
+
+
+def _stream_groups(who, ng, cdfs_all, group_cdf, init):
+    """The host-side preconditions of the mixed-stream counter."""
+    total = lib().rv_ec_cdf_total_all()
+    cdfs = np.ascontiguousarray(cdfs_all, np.uint16)
+    if cdfs.size == 0 or cdfs.size % total or (cdfs.ndim > 1 and cdfs.shape[-1] != total):
+        raise Rav1eHipError(f"{who}: snapshots are rv_ec_cdf_total_all() = {total} u16 wide")
+    cdfs = cdfs.reshape(-1, total)
+    gc = None if group_cdf is None else np.ascontiguousarray(group_cdf, np.int32).ravel()
+    ini = None if init is None else np.ascontiguousarray(init, np.uint32).ravel()
+    if (gc is not None and len(gc) != ng) or (ini is not None and len(ini) != ng):
+        raise Rav1eHipError(f"{who}: group_cdf / init need one entry per group")
+    return cdfs, gc, ini
+
+
+def _upload_snapshots(cdfs, phase):
+    """cdfs on the device, displaced by `phase` u16: (buffer, pointer)"""
+    flat = np.concatenate([np.zeros(int(phase), np.uint16), cdfs.ravel()])
+    buf = DeviceBuffer.from_array(flat)
+    return buf, buf.ptr + 2 * int(phase)
+
+
+def ec_rate_stream_batch(tokens, offsets, group_first, cdfs_all, group_cdf=None, init=None,
+                         waves=None, cdf_phase=0):
+    """rv_ec_rate_stream_batch: ec_rate_batch over the combined table and mixed
+    tokens (symbols of both parts, raw bits, the frame-edge partition token).
+    cdfs_all: (n_cdfs, rv_ec_cdf_total_all()) u16.  waves: groups per workgroup
+    (1, 2, 4; None: the library's choice).  cdf_phase: u16 the snapshot table
+    is displaced by on the device (its 16-byte phase).  Returns (rates u32 per
+    group, d_status[0], the snapshots as the device holds them afterwards)."""
+    def dev(x, dt):
+        return x if isinstance(x, DeviceBuffer) else DeviceBuffer.from_array(np.asarray(x, dt))
+    group_first = np.ascontiguousarray(group_first, np.int32)
+    ng = len(group_first) - 1
+    if ng < 0:
+        raise Rav1eHipError("ec_rate_stream_batch: group_first needs n_groups + 1 entries")
+    if waves not in (None, 1, 2, 4):
+        raise Rav1eHipError("ec_rate_stream_batch: waves is 1, 2 or 4")
+    cdfs, gc, ini = _stream_groups("ec_rate_stream_batch", ng, cdfs_all, group_cdf, init)
+    dtok, doff = dev(tokens, np.uint32), dev(offsets, np.uint32)
+    dgf = DeviceBuffer.from_array(group_first)
+    dcdf, pcdf = _upload_snapshots(cdfs, cdf_phase)
+    dgc = None if gc is None or ng == 0 else DeviceBuffer.from_array(gc)
+    dini = None if ini is None or ng == 0 else DeviceBuffer.from_array(ini)
+    drate, dst = DeviceBuffer(4 * max(ng, 1)), DeviceBuffer(4)
+    args = (dtok.ptr, doff.ptr, dgf.ptr, ng, pcdf, len(cdfs), dgc.ptr if dgc else None,
+            dini.ptr if dini else None, drate.ptr, dst.ptr)
+    if waves is None:
+        _check(lib().rv_ec_rate_stream_batch(*args, None), "rv_ec_rate_stream_batch")
+    else:
+        _check(lib().rv_ec_rate_stream_batch_waves(*args, int(waves), None),
+               "rv_ec_rate_stream_batch")
+    _sync(None)
+    after = dcdf.download(np.uint16)[int(cdf_phase):].reshape(cdfs.shape)
+    return drate.download(np.uint32, ng), int(dst.download(np.uint32)[0]), after
+
+
+def _mode_job_record(x):
+    if isinstance(x, np.void) or (isinstance(x, np.ndarray) and x.dtype == EC_MODE_JOB):
+        return np.array(x, EC_MODE_JOB).reshape(-1)[0]
+    return ec_mode_jobs(np.asarray(x, np.int64).reshape(1, -1))[0]
+
+
+def pack_candidates(candidates, check=True):
+    """candidates: (part, block, tx) triples.  part: the candidate's partition
+    node (an EC_MODE_JOB record or row of kind 1, where the reference writes
+    one: bsize >= BLOCK_8X8 && is_sqr) or None; block: its block (kind 0); tx:
+    its transform blocks, code_coefficients' rows of kind 0 (luma then chroma
+    in write_tx_tree / write_tx_blocks' order; none for a skip block).  Raises
+    for a candidate without a block and, with check, where the reference would
+    panic (check_mode_jobs) or a transform block lies outside its block.
+    Returns (EC_CAND array, EC_MODE_JOB array, tx rows (k, 10), each row's tile)."""
+    cands, mjobs, rows, tiles = [], [], [], []
+    for i, cand in enumerate(candidates):
+        if len(cand) != 3:
+            raise Rav1eHipError(f"candidate {i}: (partition node or None, block, transform blocks)")
+        part, block, tx = cand
+        if block is None:
+            raise Rav1eHipError(f"candidate {i} has no block")
+        blk = _mode_job_record(block)
+        if check and int(blk["kind"]) != 0:
+            raise Rav1eHipError(f"candidate {i} has no block")
+        pi = -1
+        if part is not None:
+            pi = len(mjobs)
+            mjobs.append(_mode_job_record(part))
+        bi = len(mjobs)
+        mjobs.append(blk)
+        tx = np.asarray(tx if tx is not None else [], np.int64).reshape(-1, 10)
+        n4 = _BSIZE_N4.get(int(blk["bsize"]))
+        if check and len(tx) and n4 is not None:
+            bx, by = int(blk["bx"]), int(blk["by"])
+            inside = (tx[:, 0] == 0) & (tx[:, 2] >= bx) & (tx[:, 2] < bx + n4) & \
+                (tx[:, 3] >= by) & (tx[:, 3] < by + n4)
+            if not inside.all() or int(blk["skip"]):
+                raise Rav1eHipError(f"candidate {i}: transform jobs outside the block")
+        cands.append((pi, bi, len(rows), len(tx)))
+        rows += tx.tolist()
+        tiles += [int(blk["tile"])] * len(tx)
+    mj = np.array(mjobs, EC_MODE_JOB) if mjobs else np.zeros(0, EC_MODE_JOB)
+    if check:
+        check_mode_jobs(mj)
+    return (np.array(cands, EC_CAND) if cands else np.zeros(0, EC_CAND), mj,
+            np.array(rows, np.int64).reshape(-1, 10), np.array(tiles, np.int32))
+
+
+class EcCodingState:
+    """The coding state candidates are priced against: the neighbour-record
+    map rv_ec_mode_tokenize and the coefficient-context map rv_ec_tokenize
+    leave behind after the committed jobs (one tile list, code_tile's job
+    formats; coefficient rows of kind 3 start the tiles in the mode jobs'
+    `tile` order), and the coefficients on the device.  Candidates only read
+    it.  Maps built from more blocks than those before a candidate give the
+    same tokens, so one state serves a frame."""
+
+    def __init__(self, mode_jobs, coeff_jobs, coeffs, params, xdec=1, ydec=1):
+        mode_jobs = np.ascontiguousarray(mode_jobs, EC_MODE_JOB)
+        self.params, self.xdec, self.ydec = params, int(xdec), int(ydec)
+        dims = params.tile_dims
+        self.ntiles = len(dims)
+        _, _, bad, self.mode_map, (self.mw8, self.mh8), self.ddim = _ec_mode_tokenize(mode_jobs,
+                                                                                      params)
+        if bad:
+            raise Rav1eHipError(f"EcCodingState: {bad} mode jobs outside the tokenizer's restrictions")
+        # a 64x64 candidate at the last superblock may hang over the tile's edge
+        cover = tuple(int(-(-int(dims[:, k].max()) // 16) * 16) for k in range(2))
+        tk = _EcTokens(coeff_jobs, coeffs, self.xdec, self.ydec, "EcCodingState",
+                       min_tiles=self.ntiles, min_map=cover)
+        self.coef_map, self.mw4, self.mh4, self.co = tk.dmap, tk.mw, tk.mh, tk.co
+
+    def mode_map_host(self):
+        return self.mode_map.download(np.uint32)
+
+    def coef_map_host(self):
+        return self.coef_map.download(np.uint8)
+
+
+def _run_candidates(who, state, candidates, check, rate_args):
+    cands, mj, rows, tiles = pack_candidates(candidates, check)
+    n, ntx = len(cands), len(rows)
+    if rate_args is not None:
+        cdfs, gc, ini = _stream_groups(who, n, *rate_args)
+    ej = np.zeros(ntx, EC_JOB)
+    for k, f in enumerate(["kind", "plane", "bx", "by", "tx_size", "tx_type", "is_inter", "bw_lg",
+                           "bh_lg"]):
+        ej[f] = rows[:, k]
+    ej["tile"] = tiles
+    ej["coeffs"] = state.co.ptr + 4 * rows[:, 9].astype(np.uint64)
+    area = np.where((rows[:, 4] >= 0) & (rows[:, 4] <= 4), 16 << (2 * np.clip(rows[:, 4], 0, 3)), 0)
+    cap = int(160 * n + 64 * ntx + 8 * int(area.sum()) + 1024)
+    L = lib()
+    dc = DeviceBuffer.from_array(cands) if n else None
+    dm = DeviceBuffer.from_array(mj) if len(mj) else None
+    dt = DeviceBuffer.from_array(ej) if ntx else None
+    scr = DeviceBuffer(L.rv_ec_cand_scratch_bytes(n, ntx) + 16)
+    doff, dtok, dst = DeviceBuffer(4 * (n + 1)), DeviceBuffer(4 * cap), DeviceBuffer(16)
+    head = (dc.ptr if dc else None, n, dm.ptr if dm else None, len(mj), dt.ptr if dt else None, ntx,
+            state.params.c_struct(), state.ntiles, state.ddim.ptr, state.xdec, state.ydec,
+            state.mw4, state.mh4, state.coef_map.ptr, state.mw8, state.mh8, state.mode_map.ptr,
+            scr.ptr, doff.ptr, dtok.ptr, cap)
+    rates = None
+    if rate_args is None:
+        _check(L.rv_ec_cand_tokenize(*head, dst.ptr, None), "rv_ec_cand_tokenize")
+    else:
+        dcdf = DeviceBuffer.from_array(cdfs)
+        dgc = None if gc is None or n == 0 else DeviceBuffer.from_array(gc)
+        dini = None if ini is None or n == 0 else DeviceBuffer.from_array(ini)
+        drate = DeviceBuffer(4 * max(n, 1))
+        _check(L.rv_ec_cand_rates(*head, dcdf.ptr, len(cdfs), dgc.ptr if dgc else None,
+                                  dini.ptr if dini else None, drate.ptr, dst.ptr, None),
+               "rv_ec_cand_rates")
+    _sync(None)
+    status = dst.download(np.uint32)
+    if status[1]:
+        raise Rav1eHipError(f"{who}: token buffer overflow")
+    if rate_args is not None:
+        rates = drate.download(np.uint32, n)
+    tok = dtok.download(np.uint32)[:int(status[0])]
+    off = doff.download(np.uint32)[:n + 1]
+    return rates, tok, off, int(status[2]), int(status[3]) if rate_args is not None else 0
+
+
+def ec_tokenize_candidates(state, candidates, check=True):
+    """rv_ec_cand_tokenize: every candidate's tokens (partition, pre_cdef, the
+    mode symbols of post_cdef, the coefficient tokens) against an
+    EcCodingState, which is not changed.  candidates: pack_candidates' triples,
+    the transform rows' coeff_off into the state's coefficients.  check: raise
+    where the reference would panic; without it the device counts such
+    candidates.  Returns (tokens u32, offsets u32 [n + 1], rejected candidates)."""
+    _, tok, off, rejected, _ = _run_candidates("ec_tokenize_candidates", state, candidates, check,
+                                               None)
+    return tok, off, rejected
+
+
+def ec_candidate_rates(state, candidates, cdfs_all, group_cdf=None, init=None, check=True):
+    """rv_ec_cand_rates against an EcCodingState: (rates, tokens, offsets,
+    rejected candidates, counter groups that hit a bad token or snapshot)."""
+    return _run_candidates("ec_candidate_rates", state, candidates, check,
+                           (cdfs_all, group_cdf, init))
+
+
+def candidate_rates(committed_mode_jobs, committed_coeff_jobs, coeffs, candidates, params, cdfs_all,
+                    group_cdf=None, init=None, xdec=1, ydec=1):
+    """What wr.tell_frac() - tell is in luma_chroma_mode_rdo (src/rdo.rs:689-768)
+    for every candidate: the committed jobs build the two context maps
+    (ec_tokenize_modes' and code_coefficients' job formats), each candidate's
+    partition node, mode info and coefficients are tokenized against them and
+    counted from a private copy of snapshot group_cdf[c] (default 0) of cdfs_all
+    and the writer state init[c] (rng | (cnt & 0xFFFF) << 16; default fresh).
+    coeffs: the coefficients of the committed and the candidates' transform
+    rows.  Returns (rates in 1 / 2**EC_BITRES bit, tokens, offsets)."""
+    cands = list(candidates)
+    # the preconditions first: nothing below needs a device to refuse them
+    pack_candidates(cands, True)
+    _stream_groups("candidate_rates", len(cands), cdfs_all, group_cdf, init)
+    state = EcCodingState(committed_mode_jobs, committed_coeff_jobs, coeffs, params, xdec, ydec)
+    rates, tok, off, rejected, bad = ec_candidate_rates(state, cands, cdfs_all, group_cdf, init)
+    if rejected or bad:
+        raise Rav1eHipError(f"candidate_rates: {rejected} candidates outside the restrictions, "
+                            f"{bad} groups with a bad token or snapshot index")
+    return rates, tok, off
 
 
 def prep_8tap_batch(src: DevicePlane, jobs, w, h, mode_x=0, mode_y=0, bit_depth=8):

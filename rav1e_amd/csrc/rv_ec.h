@@ -132,9 +132,48 @@ __host__ __device__ inline bool ec_token_ok(uint32_t t, int total, int &off, int
   return !(off + len > total || len < 2 || s >= len - 1);
 }
 
+// ---- the edge token: partition_gather_vert_alike / _horz_alike
+// (src/context.rs:1995-2057), shared by the host coders (rv_ec.hip) and the
+// device counter of mixed streams (rv_ec_rate.hip).
+// The test of an edge token's fields (after ec_token_ok): gather 1 or 2, a
+// whole 10-type partition CDF of the table whose partition CDFs start at
+// `part`, the symbol is_split.
+__host__ __device__ inline bool ec_edge_ok(int gather, int off, int len, int s, int part) {
+  return !(gather < 1 || gather > 2 || len != 11 || s > 1 || off < part ||
+           off + len > part + 20 * 11 || (off - part) % 11);
+}
+// Entry e (0 .. 9) of the partition CDF c[] enters gather g with its
+// probability (e > 0 ? c[e - 1] : 32768) - c[e] when the reference's gather
+// lists it (1 vert-alike: entries 2 3 4 6 7 9, 2 horz-alike: 1 3 4 5 6 8),
+// with 0 otherwise.
+__host__ __device__ inline uint32_t ec_gather_term(int gather, int e, uint32_t prev, uint32_t cur) {
+  const uint32_t mask = gather == 1 ? 0x2DCu : 0x17Au;
+  return (mask >> e) & 1 ? prev - cur : 0u;
+}
+// The 2-entry CDF is [x, 0], x = 32768 - (32768 - the terms), in u16 arithmetic
+__host__ __device__ inline uint32_t ec_gather_x(uint32_t sum_of_terms) { return sum_of_terms & 0xFFFF; }
+// Writer::symbol(s, [x, 0]) as store()'s arguments
+__host__ __device__ inline void ec_edge_store_args(uint32_t x, int s, uint32_t &fl, uint32_t &fh,
+                                                   uint32_t &nms) {
+  fl = s ? x : 32768u;
+  fh = s ? 0u : x;
+  nms = s ? 1u : 2u;
+}
+// the serial form (host)
+inline uint32_t ec_gather_cdf(const uint16_t *c, int gather) {
+  uint32_t sum = 0;
+  for (int e = 0; e < 10; e++) sum += ec_gather_term(gather, e, e > 0 ? c[e - 1] : 32768u, c[e]);
+  return ec_gather_x(sum);
+}
+
 // exclusive scan of v[0..n) in place (rv_ec.hip); v[n] and status[0] = the total
 void ec_scan(uint32_t *v, int n, const uint32_t *dn, uint32_t *bsum, uint32_t *status,
              hipStream_t st);
+// the mixed-stream counter's launch (rv_ec_rate.hip), behind rv_ec_cand.hip's tokenizer
+int ec_rate_stream_launch(const uint32_t *d_tokens, const uint32_t *d_offsets,
+                          const int32_t *d_group_first, int n_groups, const uint16_t *d_cdfs,
+                          int n_cdfs, const int32_t *d_group_cdf, const uint32_t *d_init,
+                          uint32_t *d_rate, uint32_t *d_status, int waves, hipStream_t st);
 int ec_frame_tokens(const EcFrameArgs &a, const EcFrameBufs &b, hipStream_t st);
 // worst-case jobs of a group of nsb superblocks (8x8 leaves at 4:2:0 or
 // 64x64 leaves with four chroma transforms at 4:4:4)
