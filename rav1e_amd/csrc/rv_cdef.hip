@@ -15,6 +15,7 @@
 // Out of place: src is the unfiltered reconstruction, dst receives it
 // filtered (the reference writes back into rec from its copy).
 #include "rv_device.h"
+#include "rv_cdef.h"
 
 namespace rv {
 

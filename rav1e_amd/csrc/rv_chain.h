@@ -50,7 +50,7 @@ struct ChainNext {
 
 // Called by one thread of the workgroup that finished job `job` with its
 // best MV.  (The coarse and half-res results feed several later jobs each;
-// fill_preds_kernel in rv_replay.hip gathers those.)
+// fill_preds_kernel in rv_replay_frame.hip gathers those.)
 __device__ inline void chain_emit(const ChainNext &c, int job, int n_per_ref, int n_refs,
                                   rv_mv best) {
   (void)n_per_ref;

@@ -10,6 +10,7 @@
 // as per-4x4 bytes: log2 of the square block's width in 4x4 units and the
 // skip flag (every block inter, loop-filter deltas off).
 #include "rv_device.h"
+#include "rv_deblock.h"
 
 namespace rv {
 

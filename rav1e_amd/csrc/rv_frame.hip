@@ -1,6 +1,7 @@
 // rv_frame.hip -- frame-layout kernels: Plane::pad and
 // Plane::downsample_from (src/frame/plane.rs:269-314, 399-423).
 #include "rv_device.h"
+#include "rv_frame.h"
 
 namespace rv {
 

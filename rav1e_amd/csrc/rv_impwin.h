@@ -1,6 +1,6 @@
 // rv_impwin.h -- block importances over the lookahead window
 // (compute_block_importances, src/api/internal.rs:823-1081) for the replay's
-// lookahead engine (rv_replay.hip, RvLaEngine).
+// lookahead engine (rv_replay_la.hip, RvLaEngine).
 //
 // The reference propagates, for every frame of the window from the last one
 // down to the second, each 8x8 block's share of (intra cost + its own

@@ -19,6 +19,7 @@
 
 #include "rv_chain.h"
 #include "rv_device.h"
+#include "rv_me.h"
 
 namespace rv {
 

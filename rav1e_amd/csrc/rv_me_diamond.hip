@@ -29,6 +29,7 @@
 
 #include "rv_chain.h"
 #include "rv_device.h"
+#include "rv_me.h"
 
 namespace rv {
 

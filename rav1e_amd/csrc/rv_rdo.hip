@@ -1544,7 +1544,7 @@ static void rdo_launch(const RdoArgs &luma, const RdoArgs &chroma, int hbd, hipS
     rdo_quad_kernel<uint8_t, MODE><<<grid, 256, 0, s>>>(luma, chroma, nquads, kRdoVariant);
 }
 
-// Replay-internal entry (rv_replay.hip): luma (N = 64, cdef distortion)
+// Replay-internal entry (rv_replay_frame.hip): luma (N = 64, cdef distortion)
 // and both chroma planes (N = 32, SSE) of every task, one launch on `s`.
 // compound: the tasks are compound candidates (score launches only).
 int rv_rdo_candidates(const RdoArgs &luma, const RdoArgs &chroma, int hbd, hipStream_t s,

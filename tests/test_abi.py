@@ -100,7 +100,7 @@ def test_no_device_here_fails_loudly():
 
 
 def test_round_ring_slots_keep_live_checks_apart():
-    """The MV-stack / lookahead round loop (rv_replay.hip run_rounds) keeps
+    """The MV-stack / lookahead round loop (rv_replay.h run_rounds) keeps
     kRoundsAhead rounds queued beyond the last published count it read, so
     up to kRoundsAhead + 2 checks are in flight at once.  Their device count
     slots, the slot each zeroes for its successor and their host

@@ -878,7 +878,7 @@ def test_gpu_paired_replay_matches_cpu(flags, window, ready, twin):
 @pytest.mark.gpu
 @pytest.mark.parametrize("flags", [0, RP.RV_REPLAY_DEBLOCK | RP.RV_REPLAY_CDEF | RP.RV_REPLAY_SPEED6, _LRF])
 def test_gpu_replay_one_rank_rccl_exchange(flags):
-    """The RCCL branch of the tile-group exchange (rv_replay.hip: pack,
+    """The RCCL branch of the tile-group exchange (rv_replay_frame.hip finish_slot: pack,
     ncclAllGather on the replay stream, import, loop filters, pad) with a
     1-rank communicator (rv_comm_unique_id / rv_comm_create): the words and
     every reconstruction equal the run without a communicator."""
