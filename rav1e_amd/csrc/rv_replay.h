@@ -1,8 +1,9 @@
 // rv_replay.h -- internal: what the replay's three files share.  The constants
 // and geometry helpers, the instance (rv_replay) with its DPB slots, round
-// ring, lookahead engine and entropy host thread, the round loop's host
-// side (run_rounds), the names of the timing events, and the host functions
-// one file defines and another calls.  rv_replay.hip: create / destroy, job
+// ring, lookahead engine and entropy host thread (an Owned, rv_owned.h, holds
+// what the runtime hands out to them), the round loop's host side
+// (run_rounds), the names of the timing events, and the host functions one
+// file defines and another calls.  rv_replay.hip: create / destroy, job
 // tables, setters, getters, read-outs; rv_replay_frame.hip: one coded frame;
 // rv_replay_la.hip: the lookahead and its engine.
 #pragma once
@@ -26,6 +27,7 @@
 #include "rv_intra_pass.h"
 #include "rv_me.h"
 #include "rv_mvref.h"
+#include "rv_owned.h"
 #include "rv_impwin.h"
 #include "rv_lrf.h"
 #include "rv_rdo.h"
@@ -294,6 +296,7 @@ struct RvLaEngine {
   static constexpr int kLaSlack = 28;
   int W = 0, RW = 0, dev = 0;
   long limit = 0;  // coded frames in the stream (0: unbounded)
+  Owned own;  // its stream, events (its hub events too), pinned ring; its device arrays are the replay's
   hipStream_t las = nullptr;  // the engine's stream: the searches and the window passes
   RoundRing rr;
   int32_t *la_list = nullptr;
@@ -337,37 +340,39 @@ struct RvLaEngine {
   long data_ready = 0, xchg_done = 0, xchg_next = 1;
   rv_la_hub *hub = nullptr;
   int hub_k = -1;
-  std::vector<hipEvent_t> hub_ev;  // this member's hub events (destroyed with the engine)
   Entry &at(long m) { return ring[(size_t)(m % RW)]; }
 };
 
 struct rv_replay {
-  rv_replay_cfg cfg;
-  Geo g;
+  rv_replay_cfg cfg{};
+  Geo g{};
   int RA = 1;  // the lookahead's references (LaRefs; R = 2: 3, LAST3 added)
-  CandGeo cg;
-  hipStream_t stream;
+  CandGeo cg{};
+  Owned own;  // every device / pinned allocation, event and stream of the instance
+  hipStream_t stream = nullptr;
+  template <class T>  // a device array, the fill queued on the stream
+  T *dev(size_t n, Fill fill = Fill::None) { return own.dev<T>(n, fill, stream); }
   hipEvent_t ev_ielig = nullptr;  // intra_begin's count is on the host
   // the frame-edge levels get a stream of their own (edge, below);
   // RAV1E_HIP_REPLAY_SERIAL=1: one stream (the profiling mode)
   bool overlap = false;
-  bool own_stream;
-  bool sea;  // successive-elimination coarse search (bit depth <= 10)
+  bool own_stream = false;  // (the caller's stream is not in `own`)
+  bool sea = false;  // successive-elimination coarse search (bit depth <= 10)
   // per pyramid level: the frame's quantizers (QuantizationContext of
   // TX_64X64 luma / TX_32X32 chroma, inter) and lambdas
   struct Level {
     bool set = false;
-    int qidx;
-    QCtx ql, qu, qv;
-    QCtx qil, qiu, qiv;   // the same transforms, intra (is_intra rounding)
-    QCtx qs[kLevels][3];  // speed 6: luma / U / V of the 32x32 .. 8x8 blocks
-    double lambda, me_lambda, ds[3];
-  } lv[3];
+    int qidx = 0;
+    QCtx ql{}, qu{}, qv{};
+    QCtx qil{}, qiu{}, qiv{};  // the same transforms, intra (is_intra rounding)
+    QCtx qs[kLevels][3] = {};  // speed 6: luma / U / V of the 32x32 .. 8x8 blocks
+    double lambda = 0.0, me_lambda = 0.0, ds[3] = {0.0, 0.0, 0.0};
+  } lv[3] = {};
   // speed 6: the partition levels below 64x64 (index 0 = the superblocks,
   // whose arrays are the ones above)
   struct PLevel {
-    int B, n, gw, gh, bc, bch, txl, txc;
-    CandGeo cg;
+    int B = 0, n = 0, gw = 0, gh = 0, bc = 0, bch = 0, txl = 0, txc = 0;
+    CandGeo cg{};
     rv_ds_job *jobs_full[3] = {nullptr, nullptr, nullptr}, *jobs_sub[3] = {nullptr, nullptr, nullptr};
     rv_fs_result *full = nullptr, *sub = nullptr;
     uint64_t *l_out = nullptr, *c_out = nullptr;
@@ -376,7 +381,7 @@ struct rv_replay {
     int32_t *l_lev = nullptr, *c_lev = nullptr;
     int32_t *leaf = nullptr;
     size_t woff = 0;  // result words offset
-  } pl[kLevels];
+  } pl[kLevels] = {};
   bool s6 = false;
   // the 32x32 .. 8x8 level grids: speed 6 over the group, speed 10 over the
   // bounding rectangle (group superblocks ex0, ey0 + ew x eh) of the
@@ -406,8 +411,8 @@ struct rv_replay {
   uint64_t *lrf_err = nullptr;
   int8_t *lrf_xqd = nullptr, *lrf_units = nullptr;
   int lrf_fix_passes = 1 << 30;  // the decision kernel (create: RAV1E_LRF_FIX[_PASSES])
-  RvInput lrf_out;
-  RvInput cdef_pre;                 // the deblocked, pre-CDEF frame (the padded copy's source)
+  RvInput lrf_out{};
+  RvInput cdef_pre{};                // the deblocked, pre-CDEF frame (the padded copy's source)
   uint8_t *cdef_dir = nullptr, *cdef_idx = nullptr;  // per 8x8 block; per 64x64 (all 0)
   int32_t *cdef_var = nullptr;
   uint8_t cdef_str[3][2] = {};      // [level] = (y, uv) strengths at cdef_index 0
@@ -446,12 +451,11 @@ struct rv_replay {
   std::mutex jobs_mu;  // ensure_jobs: the encode and the lookahead engine may both need them
   std::vector<RvSlot> slots;
   std::vector<RvInput> inputs;
-  std::vector<void *> allocs;
   rv_fs_job *fs_jobs[3] = {nullptr, nullptr, nullptr};  // per level (scale 4, 2, 1)
-  rv_fs_result *coarse, *half, *full, *sub;  // half: 4 quadrants per superblock
-  rv_fs_result *look;                         // lookahead: 16 16x16 blocks per superblock
+  // half: 4 quadrants per superblock; look(ahead): 16 16x16 blocks per superblock
+  rv_fs_result *coarse = nullptr, *half = nullptr, *full = nullptr, *sub = nullptr, *look = nullptr;
   rv_fs_result *half_l = nullptr;             // the lookahead's 4 quadrants per superblock
-  rv_ds_job *jobs_half[3], *jobs_full[3], *jobs_sub[3], *jobs_look[3];  // per level
+  rv_ds_job *jobs_half[3] = {}, *jobs_full[3] = {}, *jobs_sub[3] = {}, *jobs_look[3] = {};  // per level
   rv_ds_job *jobs_half_l[3] = {nullptr, nullptr, nullptr};  // the lookahead's F2 (per level)
   int32_t *la_list = nullptr;  // the lookahead rounds' marked jobs: F2 [R nsb 4], then FL [R nsb 16]
   long la_round_sum = 0, la_reeval = 0;  // the lookahead rounds (round 0 included), re-evaluated jobs
@@ -460,24 +464,24 @@ struct rv_replay {
   bool eng_owned = false;     // the primary owns it; a twin borrows it
   const float *imp_last = nullptr;  // the importances the last coded frame used
   int32_t *src_half = nullptr, *src_full = nullptr, *src_look = nullptr;  // predictor sources
-  uint64_t *l_out, *c_out;  // F4: [skip dist, non-skip dist, rate] per transform block
-  RdoWinner *win;
-  int32_t *cand_list, *cand_count;  // F4: the valid candidates
+  uint64_t *l_out = nullptr, *c_out = nullptr;  // F4: [skip dist, non-skip dist, rate] per tx block
+  RdoWinner *win = nullptr;
+  int32_t *cand_list = nullptr, *cand_count = nullptr;  // F4: the valid candidates
   RdoArgs *f4_args = nullptr;        // F4: the frame's list-launch arguments [la, ca, lc, cc]
   CandKey *cand_key = nullptr;       // F4: what each candidate slot was last evaluated with
   uint8_t *f3dirty = nullptr;        // rounds: the F3 jobs whose set / pmv changed [R][nsb]
   uint8_t *f2dirty = nullptr;        // rounds: the F2 jobs whose set changed [R][nsb][4]
-  uint32_t *cand_evals;  // [kRing][2 * kLevels]: F4 candidates per frame and level (single, compound)
-  int32_t *l_lev, *c_lev;   // F6: committed levels
-  uint64_t *words;
-  unsigned long long *tail;  // [levels csum, group recon sum, imp satd sum, -, frame recon sum]
+  uint32_t *cand_evals = nullptr;  // [kRing][2 * kLevels]: F4 candidates per frame and level (single, compound)
+  int32_t *l_lev = nullptr, *c_lev = nullptr;  // F6: committed levels
+  uint64_t *words = nullptr;
+  unsigned long long *tail = nullptr;  // [levels csum, group recon sum, imp satd sum, -, frame recon sum]
   float *imp = nullptr;      // block_importances (null: all zero)
-  int n_imp, imp_bx, imp_by, ntx_c;
+  int n_imp = 0, imp_bx = 0, imp_by = 0, ntx_c = 0;
   long coded = 0;            // frames coded so far (0 = the key frame next)
   rv_replay_frame_info last{};
   // tile-group exchange (F7)
   int n_groups = 1, my_group = 0;
-  int32_t grects[4 * kMaxGroups];
+  int32_t grects[4 * kMaxGroups] = {};
   size_t xbytes = 0;         // packed bytes per group (the largest group)
   uint8_t *xsend = nullptr, *xrecv = nullptr;
   void *comm = nullptr;      // ncclComm_t (rv_comm)
@@ -486,11 +490,11 @@ struct rv_replay {
   // frame.  Every `timing_stride`-th block of frames is instrumented (each
   // record costs ~4.4 us of idle GPU between kernels on MI355X).
   static constexpr int kRing = 64;
-  hipEvent_t evs[kRing][kEvCount];  // StageEv
+  hipEvent_t evs[kRing][kEvCount] = {};  // StageEv
   int timing_stride = 1, timing_block = 1;
   long timed = 0;
   // diamond candidate evaluations per job, per ring slot: [kRing][2][nsb*R]
-  uint32_t *ds_evals;
+  uint32_t *ds_evals = nullptr;
   // Kernel probes (rv_replay_set_kernel_probe): on instrumented frames
   // every launch of a probed kernel -- probe 0: F3 sub-pel
   // (ds_fast_kernel<W = H = 64, sub-pel>), probe 1: the F4 candidate lists
@@ -577,10 +581,9 @@ namespace rv {
 inline bool groups_active(const rv_replay *r) { return r->n_groups >= 2 || r->comm; }
 
 // rv_replay.hip
-void *dalloc(rv_replay *r, size_t bytes);
 hipError_t kp_harvest(rv_replay *r, int p, long upto);
 size_t plane_bytes(const rv_plane &p);
-bool round_ring_alloc(rv_replay *r, RoundRing &q, hipStream_t st);
+void round_ring_alloc(Owned &dev, Owned &host, RoundRing &q, hipStream_t st);
 int ensure_jobs(rv_replay *r);
 int group_rects(const rv_replay *r, int k, XRect out[9], int *n);
 int xcopy(rv_replay *r, const RvSlot &s, const XRect *rects, int n, int to_plane, uint8_t *buf);

@@ -169,13 +169,6 @@ void EcHost::drain() {
 
 namespace rv {
 
-void *dalloc(rv_replay *r, size_t bytes) {
-  void *p = nullptr;
-  if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-  r->allocs.push_back(p);
-  return p;
-}
-
 // kernel probe p's pairs [kp_done, upto): their elapsed times and device
 // spans summed (the spans in at most two copies)
 hipError_t kp_harvest(rv_replay *r, int p, long upto) {
@@ -216,69 +209,60 @@ size_t frame_planes(const Geo &g, rv_plane &y, rv_plane &u, rv_plane &v) {
 }
 size_t plane_bytes(const rv_plane &p) { return (size_t)p.stride * p.alloc_height * (p.hbd ? 2 : 1); }
 
-bool alloc_input(rv_replay *r, RvInput &in, bool pyramid) {
+// One zeroed block per input / DPB slot, carved at 256-byte steps (a failed
+// allocation latches in r->own)
+static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+static uint8_t *carve(uint8_t *&m, size_t bytes) {
+  uint8_t *p = m;
+  m += up256(bytes);
+  return p;
+}
+
+void alloc_input(rv_replay *r, RvInput &in, bool pyramid) {
   const Geo &g = r->g;
   frame_planes(g, in.y, in.u, in.v);
   const int pad = 88;
   rv_plane_geometry(&in.hres, g.W / 2, g.H / 2, 1, 1, pad / 2, pad / 2, g.hbd);
   rv_plane_geometry(&in.qres, g.W / 4, g.H / 4, 2, 2, pad / 4, pad / 4, g.hbd);
   in.hres.bit_depth = in.qres.bit_depth = g.bd;
-  const size_t al = 256;
-  auto up = [&](size_t v) { return (v + al - 1) / al * al; };
   const size_t by = plane_bytes(in.y), bu = plane_bytes(in.u);
   const size_t bh = pyramid ? plane_bytes(in.hres) : 0, bq = pyramid ? plane_bytes(in.qres) : 0;
   const size_t bs8 = pyramid ? (size_t)in.qres.stride * in.qres.alloc_height * 8 : 0;
-  const size_t total = up(by) + 2 * up(bu) + up(bh) + up(bq) + up(bs8);
-  uint8_t *m = (uint8_t *)dalloc(r, total);
-  if (!m) return false;
-  uint8_t *m0 = m;
-  in.y.data = m;
-  m += up(by);
-  in.u.data = m;
-  m += up(bu);
-  in.v.data = m;
-  m += up(bu);
-  if (pyramid) {
-    in.hres.data = m;
-    m += up(bh);
-    in.qres.data = m;
-    m += up(bq);
-    in.qres_box = (uint32_t *)m;
-  }
-  return hipMemsetAsync(m0, 0, total, r->stream) == hipSuccess;
+  uint8_t *m = r->dev<uint8_t>(up256(by) + 2 * up256(bu) + up256(bh) + up256(bq) + up256(bs8),
+                               Fill::Zero);
+  if (!m) return;
+  in.y.data = carve(m, by);
+  in.u.data = carve(m, bu);
+  in.v.data = carve(m, bu);
+  if (!pyramid) return;
+  in.hres.data = carve(m, bh);
+  in.qres.data = carve(m, bq);
+  in.qres_box = (uint32_t *)m;
 }
 
-bool alloc_slot(rv_replay *r, RvSlot &s) {
+void alloc_slot(rv_replay *r, RvSlot &s) {
   const Geo &g = r->g;
   frame_planes(g, s.y, s.u, s.v);
-  const size_t al = 256;
-  auto up = [&](size_t v) { return (v + al - 1) / al * al; };
   const size_t by = plane_bytes(s.y), bu = plane_bytes(s.u);
   const size_t bf = (size_t)(g.w_in_b / 2) * (g.h_in_b / 2) * g.R * sizeof(rv_mv);
-  const size_t total = up(by) + 2 * up(bu) + up(bf);
-  uint8_t *m = (uint8_t *)dalloc(r, total);
-  if (!m) return false;
-  s.y.data = m;
-  m += up(by);
-  s.u.data = m;
-  m += up(bu);
-  s.v.data = m;
-  m += up(bu);
+  uint8_t *m = r->dev<uint8_t>(up256(by) + 2 * up256(bu) + up256(bf), Fill::Zero);
+  if (!m) return;
+  s.y.data = carve(m, by);
+  s.u.data = carve(m, bu);
+  s.v.data = carve(m, bu);
   s.fmv = (rv_mv *)m;
-  return hipMemsetAsync(s.y.data, 0, total, r->stream) == hipSuccess;
 }
 
-bool round_ring_alloc(rv_replay *r, RoundRing &q, hipStream_t st) {
-  const size_t b = RoundRing::kCnt * 8 + 4;
-  q.cnt = (int32_t *)dalloc(r, b);
-  if (!q.cnt || hipMemsetAsync(q.cnt, 0, b, st) != hipSuccess) return false;
+// A round ring: the device counts (zeroed on st) from `dev`, the host-mapped
+// publication ring from `host` (the engine's ring: the replay's, its own)
+void round_ring_alloc(Owned &dev, Owned &host, RoundRing &q, hipStream_t st) {
+  q.cnt = dev.dev<int32_t>(2 * RoundRing::kCnt + 1, Fill::Zero, st);
+  q.h_pub = host.pinned<unsigned long long>(RoundRing::kPub,
+                                            hipHostMallocMapped | hipHostMallocCoherent);
+  if (!q.cnt || !q.h_pub) return;
   q.ticket = (uint32_t *)(q.cnt + 2 * RoundRing::kCnt);
-  if (hipHostMalloc((void **)&q.h_pub, RoundRing::kPub * 8,
-                    hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer((void **)&q.d_pub, q.h_pub, 0) != hipSuccess)
-    return false;
+  if (hipHostGetDevicePointer((void **)&q.d_pub, q.h_pub, 0) != hipSuccess) host.failed = true;
   for (int i = 0; i < RoundRing::kPub; i++) q.h_pub[i] = ~0ull;
-  return true;
 }
 
 int build_static_jobs(rv_replay *r) {
@@ -286,7 +270,7 @@ int build_static_jobs(rv_replay *r) {
   auto mx = [](int a, int b) { return a > b ? a : b; };
   auto mn = [](int a, int b) { return a < b ? a : b; };
   auto upload = [&](auto &vec, auto *&dst) -> int {
-    if (!dst) dst = (std::remove_reference_t<decltype(dst)>)dalloc(r, vec.size() * sizeof(vec[0]));
+    if (!dst) dst = r->dev<std::decay_t<decltype(vec[0])>>(vec.size());
     if (!dst) return RV_EHIP;
     return hipMemcpy(dst, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice) ==
                    hipSuccess
@@ -748,64 +732,155 @@ LaRefs la_refs_of(long m, int R) {
   return l;
 }
 
-}  // namespace rv
-
-extern "C" {
-
-void rv_replay_destroy(rv_replay *r) {
-  if (!r) return;
-  la_engine_destroy(r);  // its thread first: it launches on the replay's arrays
-  // the streams drain before anything they may still read is freed
-  if (r->stream) (void)hipStreamSynchronize(r->stream);
-  if (r->ech) {  // the host coder finishes the frames it holds, then stops
-    {
-      std::lock_guard<std::mutex> lk(r->ech->mu);
-      r->ech->stop = true;
+// Where the 32x32 .. 8x8 levels run (s6, lvl, the rectangle ex0, ey0 + ew x
+// eh), which of them hold leaves / search motion, their grids over that
+// rectangle and the layout of the result words.
+static int configure_levels(rv_replay *r) {
+  const Geo &g = r->g;
+  r->nwords = (size_t)g.nsb * (kWordsPerRef * g.R + 4);
+  if (r->cfg.flags & RV_REPLAY_SPEED6) {
+    if (g.xdec != g.ydec)
+      return rv_set_error(RV_EINVAL, "rv_replay_create: speed 6 needs 4:2:0 or 4:4:4");
+    r->s6 = true;
+    r->lvl = true;
+    r->ew = g.tw;
+    r->eh = g.th;
+    for (int l = 1; l < kLevels; l++) r->lv_used[l] = true;  // every level holds leaves
+  } else if (g.xdec == g.ydec) {
+    // speed 10: encode_partition_topdown's must_split (src/encoder.rs:2407-
+    // 2445) at the frame edges, over the bounding rectangle of the group's
+    // superblocks past the right / bottom edge; the levels holding leaves are
+    // those of the must_split walk of these superblocks (largest blocks inside)
+    int x0 = g.tw, y0 = g.th, x1 = -1, y1 = -1;
+    for (int sb = 0; sb < g.nsb; sb++) {
+      const int sx = sb % g.tw, sy = sb / g.tw, X = (g.tx0 + sx) * kSb, Y = (g.ty0 + sy) * kSb;
+      if (X + kSb <= g.W && Y + kSb <= g.H) continue;
+      x0 = std::min(x0, sx);
+      y0 = std::min(y0, sy);
+      x1 = std::max(x1, sx);
+      y1 = std::max(y1, sy);
+      for (int l = 1; l < kLevels; l++) {
+        const int B = kSb >> l;
+        for (int y = Y; y < Y + kSb; y += B)
+          for (int x = X; x < X + kSb; x += B) {
+            const int inside = x + B <= g.W && y + B <= g.H;
+            const int pin = (x & ~(2 * B - 1)) + 2 * B <= g.W && (y & ~(2 * B - 1)) + 2 * B <= g.H;
+            if (inside && !pin) r->lv_used[l] = true;  // a leaf: inside, its parent is not
+          }
+      }
     }
-    r->ech->cv.notify_all();
-    if (r->ech->th.joinable()) r->ech->th.join();
-    for (int k = 0; k < 2; k++) {
-      if (r->ech->tok_h[k]) (void)hipHostFree(r->ech->tok_h[k]);
-      if (r->ech->stat_h[k]) (void)hipHostFree(r->ech->stat_h[k]);
-      if (r->ech->ev[k]) (void)hipEventDestroy(r->ech->ev[k]);
+    if (x1 >= 0) {
+      r->lvl = true;
+      r->ex0 = x0;
+      r->ey0 = y0;
+      r->ew = x1 - x0 + 1;
+      r->eh = y1 - y0 + 1;
     }
-    delete r->ech;
-    r->ech = nullptr;
   }
-  if (r->edge[1]) (void)hipStreamSynchronize(r->edge[1]);
-  for (void *p : r->allocs) (void)hipFree(p);
-  if (r->h_cnt) (void)hipHostFree(r->h_cnt);
-  if (r->rr.h_pub) (void)hipHostFree(r->rr.h_pub);
-  for (int f = 0; f < rv_replay::kRing; f++)
-    for (int i = 0; i < kEvCount; i++)
-      if (r->evs[f][i]) (void)hipEventDestroy(r->evs[f][i]);
-  for (const auto &evs : r->kp_ev)
-    for (hipEvent_t ev : evs)
-    if (ev) (void)hipEventDestroy(ev);
-  if (r->ev_ielig) (void)hipEventDestroy(r->ev_ielig);
-  for (hipEvent_t ev : {r->ev_efork, r->ev_l1me, r->ev_epart})
-    if (ev) (void)hipEventDestroy(ev);
-  for (int l = 0; l < kLevels; l++) {
-    if (r->ev_ejoin[l]) (void)hipEventDestroy(r->ev_ejoin[l]);
-    if (r->ev_ecommit[l]) (void)hipEventDestroy(r->ev_ecommit[l]);
+  if (!r->lvl) return RV_OK;
+  r->lv_me[1] = r->lv_used[1] || r->lv_used[2] || r->lv_used[3];
+  r->lv_me[2] = r->lv_used[2];
+  r->lv_me[3] = r->lv_used[3];
+  rv_replay::PLevel &P0 = r->pl[0];
+  P0.B = kSb;
+  P0.n = g.nsb;
+  P0.gw = g.tw;
+  P0.gh = g.th;
+  for (int l = 1; l < kLevels; l++) {
+    rv_replay::PLevel &P = r->pl[l];
+    const int k = 1 << l;
+    P.B = kSb >> l;
+    P.gw = r->ew * k;
+    P.gh = r->eh * k;
+    P.n = P.gw * P.gh;
+    P.bc = P.B >> g.xdec;
+    P.bch = P.B >> g.ydec;
+    P.txl = 4 - l;                                              // TX_32X32 .. TX_8X8
+    P.txc = P.bc == 32 ? 3 : P.bc == 16 ? 2 : P.bc == 8 ? 1 : 0;  // .. TX_4X4
+    P.cg = CandGeo{P.n, P.gw, P.gh, (g.tx0 + r->ex0) * k, (g.ty0 + r->ey0) * k, g.tws * k,
+                   g.ths * k, g.R, g.M, 0};
+    P.woff = r->nwords;
+    r->nwords += (size_t)P.n * (4 * g.R + 4);
   }
-  if (r->edge[1]) (void)hipStreamDestroy(r->edge[1]);  // (the other levels alias it)
-  if (r->own_stream && r->stream) (void)hipStreamDestroy(r->stream);
-  delete r;
+  r->wpart = r->nwords;
+  r->nwords += (size_t)g.nsb;
+  return RV_OK;
 }
 
-// share: a primary instance whose DPB and inputs this one borrows
-// (rv_replay_create_twin)
-static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_replay *share) {
+// The stages the flags switch on, their host-side sizes, and the two
+// environment switches.
+static int configure_stages(rv_replay *r) {
+  const Geo &g = r->g;
+  const uint32_t flags = r->cfg.flags;
+  // intra-mode screening: speed 10 4:2:0 unless RV_REPLAY_NO_INTRA
+  r->intra = !r->s6 && !(flags & RV_REPLAY_NO_INTRA) && g.xdec == 1 && g.ydec == 1;
+  // speed 10: rav1e's MV stacks in coding-order rounds
+  r->exact = !r->s6 && !(flags & RV_REPLAY_MVREF_STANDIN);
+  // does a superblock's top-right neighbour (same tile) lie past the right
+  // frame edge, i.e. is it a must_split leaf?
+  for (int sb = 0; sb < g.nsb && r->exact && r->lvl; sb++) {
+    const int fsx = g.tx0 + sb % g.tw, fsy = g.ty0 + sb / g.tw;
+    const int t0x = fsx - fsx % g.tws;
+    const int cols = std::min(g.tws * 16, g.w_in_b - t0x * 16);
+    if ((fsx + 1) * 64 <= g.W && (fsy + 1) * 64 <= g.H && fsy % g.ths != 0 &&
+        (fsx - t0x) * 16 + 16 < cols && (fsx + 2) * 64 > g.W)
+      r->edge_tr = true;
+  }
+  if (flags & RV_REPLAY_CDEF) {
+    if (!(flags & RV_REPLAY_DEBLOCK) || (g.W & 7) || (g.H & 7))
+      return rv_set_error(RV_EINVAL, "rv_replay_create: RV_REPLAY_CDEF needs RV_REPLAY_DEBLOCK and a "
+                                     "frame size that is a multiple of 8");
+    r->cdef = true;
+  }
+  if (flags & RV_REPLAY_LRF) {
+    LrfGeo lg;
+    // (the unit size depends on the quantizer: rv_replay_set_level_params
+    // checks every level's; 100 here is the replay's default level 0)
+    if (!r->cdef || g.xdec != g.ydec ||
+        lrf_geometry(g.W, g.H, g.xdec, g.ydec, g.bd, 100, g.tws, g.ths, &lg) != RV_OK)
+      return rv_set_error(RV_EINVAL, "rv_replay_create: RV_REPLAY_LRF needs RV_REPLAY_CDEF, 4:2:0 or 4:4:4 "
+                                     "(rav1e's enable_restoration is off in 4:2:2) and units of one superblock");
+    r->lrf = true;
+    // RAV1E_LRF_FIX=0 (A/B): the one-wave serial decision; RAV1E_LRF_FIX_PASSES
+    // = 1 .. caps the fixed point's parallel passes (tests: the serial rest
+    // after the cap).  Read here, once: the worker threads of a pipelined
+    // replay must not call getenv per frame while the caller may setenv.
+    const char *fe = getenv("RAV1E_LRF_FIX"), *fp = getenv("RAV1E_LRF_FIX_PASSES");
+    r->lrf_fix_passes = (fe && fe[0] == '0') ? 0 : fp ? std::max(atoi(fp), 1) : 1 << 30;
+  }
+  r->entropy = (flags & RV_REPLAY_ENTROPY) != 0;
+  if (r->entropy && g.xdec != g.ydec)
+    return rv_set_error(RV_EINVAL, "rv_replay_create: RV_REPLAY_ENTROPY needs xdec == ydec");
+  r->deblock = (flags & RV_REPLAY_DEBLOCK) != 0;
+  if (r->deblock || r->entropy) {  // the block map
+    r->mi_cols = (g.W + 3) / 4;
+    r->mi_rows = (g.H + 3) / 4;
+    r->mi_stride = (r->mi_cols + 15) / 16 * 16;
+  }
+  if (r->entropy) {
+    EcFrameBufs &b = r->ecb;
+    b.ntiles = ((g.tw + g.tws - 1) / g.tws) * ((g.th + g.ths - 1) / g.ths);
+    b.max_jobs = ec_max_jobs(g.nsb, b.ntiles);
+    b.map_w4 = g.tws * 16;
+    b.map_h4 = g.ths * 16;
+    // one token per coded coefficient plus 4 per job covers every block
+    // whose levels stay below 3; more sets the overflow flag (an error)
+    b.cap = (uint32_t)((size_t)g.nsb * (1024 + 2 * r->ntx_c * 1024) + (size_t)b.max_jobs * 4);
+  }
+  const char *e = getenv("RAV1E_HIP_REPLAY_SERIAL");
+  r->overlap = !(e && e[0] == '1');
+  return RV_OK;
+}
+
+// Every check, in the order its message is reported, and every derived value
+// that needs no device (the frame and the tile group, a rectangle of whole tiles,
+// here).  No HIP call: a rejected configuration has touched no device.
+static int replay_configure(const rv_replay_cfg *cfg, rv_replay *r) {
   if (!cfg || cfg->width <= 0 || cfg->height <= 0 || (cfg->width & 7) || (cfg->height & 7) ||
       (cfg->bit_depth != 8 && cfg->bit_depth != 10 && cfg->bit_depth != 12) || cfg->xdec < 0 ||
       cfg->xdec > 1 || cfg->ydec < 0 || cfg->ydec > 1 || cfg->n_refs < 1 || cfg->n_refs > 2 ||
-      cfg->n_inputs < 1 || cfg->tile_w_sb < 0 || cfg->tile_h_sb < 0) {
-    rv_set_error(RV_EINVAL, "rv_replay_create: bad config");
-    return nullptr;
-  }
-  rv_replay *r = new rv_replay();
-  memset(r->evs, 0, sizeof(r->evs));
+      cfg->n_inputs < 1 || cfg->tile_w_sb < 0 || cfg->tile_h_sb < 0)
+    return rv_set_error(RV_EINVAL, "rv_replay_create: bad config");
   r->cfg = *cfg;
   Geo &g = r->g;
   g.W = cfg->width;
@@ -823,15 +898,12 @@ static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_r
   g.th = cfg->tile_h > 0 ? cfg->tile_h : sbr - g.ty0;
   g.tws = cfg->tile_w_sb > 0 ? cfg->tile_w_sb : sbc;
   g.ths = cfg->tile_h_sb > 0 ? cfg->tile_h_sb : sbr;
-  // the group is a rectangle of whole tiles
   if (g.tx0 < 0 || g.ty0 < 0 || g.tw <= 0 || g.th <= 0 || g.tx0 + g.tw > sbc ||
       g.ty0 + g.th > sbr || g.tx0 % g.tws || g.ty0 % g.ths ||
       ((g.tx0 + g.tw) % g.tws && g.tx0 + g.tw != sbc) ||
-      ((g.ty0 + g.th) % g.ths && g.ty0 + g.th != sbr)) {
-    rv_set_error(RV_EINVAL, "rv_replay_create: the tile group is not a rectangle of whole tiles");
-    delete r;
-    return nullptr;
-  }
+      ((g.ty0 + g.th) % g.ths && g.ty0 + g.th != sbr))
+    return rv_set_error(RV_EINVAL,
+                        "rv_replay_create: the tile group is not a rectangle of whole tiles");
   g.vis_w = (g.W - g.tx0 * kSb) < g.tw * kSb ? g.W - g.tx0 * kSb : g.tw * kSb;
   g.vis_h = (g.H - g.ty0 * kSb) < g.th * kSb ? g.H - g.ty0 * kSb : g.th * kSb;
   g.nsb = g.tw * g.th;
@@ -847,371 +919,230 @@ static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_r
   // 8x8 sums of 10-bit pixels fit the u16 box-sum table; 12-bit searches
   // exhaustively
   r->sea = g.bd <= 10 && (cfg->flags & RV_REPLAY_EXHAUSTIVE_FS) == 0;
-  if (stream) {
-    r->stream = (hipStream_t)stream;
-    r->own_stream = false;
-  } else {
-    r->own_stream = true;
-    if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
-      rv_set_error(RV_EHIP, "rv_replay_create: stream");
-      delete r;
-      return nullptr;
-    }
-  }
-  bool ok = true;
-  if (share) {
-    r->slots = share->slots;
-    r->inputs = share->inputs;
-  } else {
-    r->slots.resize(kSlots);
-    for (auto &s : r->slots) ok = ok && alloc_slot(r, s);
-    r->inputs.resize(cfg->n_inputs);
-    for (auto &in : r->inputs) ok = ok && alloc_input(r, in, true);
-  }
   r->ntx_c = (g.cw / 32) * (g.ch / 32);
-  const int nr = g.nsb * g.R;
-  const int64_t nc = (int64_t)g.nsb * g.C;
-  r->coarse = (rv_fs_result *)dalloc(r, nr * sizeof(rv_fs_result));
-  r->half = (rv_fs_result *)dalloc(r, nr * 4 * sizeof(rv_fs_result));
-  r->look = (rv_fs_result *)dalloc(r, nr * 16 * sizeof(rv_fs_result));
-  r->half_l = (rv_fs_result *)dalloc(r, nr * 4 * sizeof(rv_fs_result));
-  r->la_list = (int32_t *)dalloc(r, (size_t)nr * 20 * 4);
-  if (r->half_l) (void)hipMemsetAsync(r->half_l, 0, nr * 4 * sizeof(rv_fs_result), r->stream);
-  if (r->look) (void)hipMemsetAsync(r->look, 0, nr * 16 * sizeof(rv_fs_result), r->stream);
-  r->full = (rv_fs_result *)dalloc(r, nr * sizeof(rv_fs_result));
-  r->sub = (rv_fs_result *)dalloc(r, nr * sizeof(rv_fs_result));
-  r->l_out = (uint64_t *)dalloc(r, (size_t)nc * 3 * 8);
-  r->c_out = (uint64_t *)dalloc(r, (size_t)nc * r->ntx_c * 3 * 8 * 2);
-  r->win = (RdoWinner *)dalloc(r, (size_t)g.nsb * sizeof(RdoWinner));
-  r->cand_list = (int32_t *)dalloc(r, (size_t)nc * 4);
-  {  // zeroed: tag 0 matches no frame
-    const size_t kb = ((size_t)g.nsb * (g.R * g.M + kCompModes)) * sizeof(CandKey);
-    r->cand_key = (CandKey *)dalloc(r, kb);
-    ok = ok && r->cand_key && hipMemsetAsync(r->cand_key, 0, kb, r->stream) == hipSuccess;
-    r->f3dirty = (uint8_t *)dalloc(r, (size_t)g.nsb * g.R);
-    r->f2dirty = (uint8_t *)dalloc(r, (size_t)g.nsb * g.R * 4);
-    ok = ok && r->f3dirty && r->f2dirty;
-  }
-  r->cand_count = (int32_t *)dalloc(r, 8);  // [single, compound]
-  r->f4_args = (RdoArgs *)dalloc(r, 4 * sizeof(RdoArgs));
-  r->cand_evals = (uint32_t *)dalloc(r, rv_replay::kRing * 2 * kLevels * 4);
-  if (r->cand_evals)
-    (void)hipMemsetAsync(r->cand_evals, 0, rv_replay::kRing * 2 * kLevels * 4, r->stream);
-  if (r->cand_count) (void)hipMemsetAsync(r->cand_count, 0, 8, r->stream);
-  r->l_lev = (int32_t *)dalloc(r, (size_t)g.nsb * 1024 * 4);
-  r->c_lev = (int32_t *)dalloc(r, (size_t)g.nsb * r->ntx_c * 1024 * 4 * 2);
-  r->nwords = (size_t)g.nsb * (kWordsPerRef * g.R + 4);
-  if (cfg->flags & RV_REPLAY_SPEED6) {
-    if (g.xdec != g.ydec) {
-      rv_set_error(RV_EINVAL, "rv_replay_create: speed 6 needs 4:2:0 or 4:4:4");
-      rv_replay_destroy(r);
-      return nullptr;
-    }
-    r->s6 = true;
-    r->lvl = true;
-    r->ew = g.tw;
-    r->eh = g.th;
-  } else if (g.xdec == g.ydec) {
-    // speed 10: encode_partition_topdown's must_split (src/encoder.rs:2407-
-    // 2445) at the frame edges, over the bounding rectangle of the group's
-    // superblocks past the right / bottom edge
-    int x0 = g.tw, y0 = g.th, x1 = -1, y1 = -1;
-    for (int sb = 0; sb < g.nsb; sb++) {
-      const int x = sb % g.tw, y = sb / g.tw;
-      if ((g.tx0 + x + 1) * kSb <= g.W && (g.ty0 + y + 1) * kSb <= g.H) continue;
-      x0 = x < x0 ? x : x0;
-      y0 = y < y0 ? y : y0;
-      x1 = x > x1 ? x : x1;
-      y1 = y > y1 ? y : y1;
-    }
-    if (x1 >= 0) {
-      r->lvl = true;
-      r->ex0 = x0;
-      r->ey0 = y0;
-      r->ew = x1 - x0 + 1;
-      r->eh = y1 - y0 + 1;
-    }
-  }
-  if (r->lvl) {
-    // the levels holding leaves: every one at speed 6; at speed 10 those of
-    // the must_split walk of the edge superblocks (largest blocks inside)
-    for (int l = 1; l < kLevels; l++) r->lv_used[l] = r->s6;
-    if (!r->s6) {
-      for (int sb = 0; sb < g.nsb; sb++) {
-        const int X = (g.tx0 + sb % g.tw) * kSb, Y = (g.ty0 + sb / g.tw) * kSb;
-        if (X + kSb <= g.W && Y + kSb <= g.H) continue;
-        for (int l = 1; l < kLevels; l++) {
-          const int B = kSb >> l;
-          for (int y = Y; y < Y + kSb; y += B)
-            for (int x = X; x < X + kSb; x += B) {
-              const int inside = x + B <= g.W && y + B <= g.H;
-              const int pin = (x & ~(2 * B - 1)) + 2 * B <= g.W && (y & ~(2 * B - 1)) + 2 * B <= g.H;
-              if (inside && !pin) r->lv_used[l] = true;  // a leaf: inside, its parent is not
-            }
-        }
-      }
-    }
-    r->lv_me[1] = r->lv_used[1] || r->lv_used[2] || r->lv_used[3];
-    r->lv_me[2] = r->lv_used[2];
-    r->lv_me[3] = r->lv_used[3];
-    rv_replay::PLevel &P0 = r->pl[0];
-    P0.B = kSb;
-    P0.n = g.nsb;
-    P0.gw = g.tw;
-    P0.gh = g.th;
-    size_t nleaf = (size_t)g.nsb;
-    for (int l = 1; l < kLevels; l++) {
-      rv_replay::PLevel &P = r->pl[l];
-      const int k = 1 << l;
-      P.B = kSb >> l;
-      P.gw = r->ew * k;
-      P.gh = r->eh * k;
-      P.n = P.gw * P.gh;
-      P.bc = P.B >> g.xdec;
-      P.bch = P.B >> g.ydec;
-      P.txl = 4 - l;                                              // TX_32X32 .. TX_8X8
-      P.txc = P.bc == 32 ? 3 : P.bc == 16 ? 2 : P.bc == 8 ? 1 : 0;  // .. TX_4X4
-      P.cg = CandGeo{P.n, P.gw, P.gh, (g.tx0 + r->ex0) * k, (g.ty0 + r->ey0) * k, g.tws * k,
-                     g.ths * k, g.R, g.M, 0};
-      const int64_t nc = (int64_t)P.n * g.C;
-      P.full = (rv_fs_result *)dalloc(r, (size_t)P.n * g.R * sizeof(rv_fs_result));
-      P.sub = (rv_fs_result *)dalloc(r, (size_t)P.n * g.R * sizeof(rv_fs_result));
-      P.l_out = (uint64_t *)dalloc(r, (size_t)nc * 3 * 8);
-      P.c_out = (uint64_t *)dalloc(r, (size_t)nc * 3 * 8 * 2);
-      P.win = (RdoWinner *)dalloc(r, (size_t)P.n * sizeof(RdoWinner));
-      P.cand_list = (int32_t *)dalloc(r, (size_t)nc * 4);
-      P.cand_count = (int32_t *)dalloc(r, 8);
-      P.l_lev = (int32_t *)dalloc(r, (size_t)P.n * P.B * P.B * 4);
-      P.c_lev = (int32_t *)dalloc(r, (size_t)P.n * P.bc * P.bch * 4 * 2);
-      ok = ok && P.full && P.sub && P.l_out && P.c_out && P.win && P.cand_list && P.cand_count &&
-           P.l_lev && P.c_lev;
-      if (P.cand_count) (void)hipMemsetAsync(P.cand_count, 0, 8, r->stream);
-      if (P.l_lev) (void)hipMemsetAsync(P.l_lev, 0, (size_t)P.n * P.B * P.B * 4, r->stream);
-      if (P.c_lev) (void)hipMemsetAsync(P.c_lev, 0, (size_t)P.n * P.bc * P.bch * 8, r->stream);
-      P.woff = r->nwords;
-      r->nwords += (size_t)P.n * (4 * g.R + 4);
-      nleaf += (size_t)P.n;
-    }
-    r->wpart = r->nwords;
-    r->nwords += (size_t)g.nsb;
-    int32_t *lf = (int32_t *)dalloc(r, nleaf * 4);
-    r->leaf_count = (int32_t *)dalloc(r, kLevels * 4);
-    ok = ok && lf && r->leaf_count;
-    if (r->leaf_count) (void)hipMemsetAsync(r->leaf_count, 0, kLevels * 4, r->stream);
-    for (int l = 0; l < kLevels && lf; l++) {
-      r->pl[l].leaf = lf;
-      lf += r->pl[l].n;
-    }
-  }
-  r->words = (uint64_t *)dalloc(r, r->nwords * 8);
-  // intra-mode screening: speed 10 4:2:0 unless RV_REPLAY_NO_INTRA
-  r->intra = !r->s6 && !(cfg->flags & RV_REPLAY_NO_INTRA) && g.xdec == 1 && g.ydec == 1;
-  r->i_stats = (uint32_t *)dalloc(r, (size_t)rv_replay::kRing * 3 * 4);
-  ok = ok && r->i_stats && hipMemsetAsync(r->i_stats, 0, (size_t)rv_replay::kRing * 3 * 4,
-                                          r->stream) == hipSuccess;
-  if (r->intra) {
-    const size_t n = (size_t)g.nsb;
-    r->i_elig = (uint8_t *)dalloc(r, n);
-    r->i_was = (uint8_t *)dalloc(r, n);
-    r->i_win = (uint8_t *)dalloc(r, 2 * n);
-    r->i_modes = (uint8_t *)dalloc(r, 4 * n);
-    r->i_mark = (int32_t *)dalloc(r, 4 * n);
-    r->i_list[0] = (int32_t *)dalloc(r, 4 * n);
-    r->i_list[1] = (int32_t *)dalloc(r, 4 * n);
-    r->i_commit = (int32_t *)dalloc(r, 4 * n);
-    r->i_revert = (int32_t *)dalloc(r, 4 * n);
-    r->i_cnt = (int32_t *)dalloc(r, 4 * sizeof(int32_t));
-    r->i_edges = dalloc(r, n * 3 * kIntraEdge * (g.hbd ? 2 : 1));
-    r->i_lout = (uint64_t *)dalloc(r, n * 3 * 3 * 8);
-    r->i_cout = (uint64_t *)dalloc(r, n * 6 * 3 * 8 * 2);
-    ok = ok && r->i_elig && r->i_was && r->i_win && r->i_modes && r->i_mark && r->i_list[0] &&
-         r->i_list[1] && r->i_commit && r->i_revert && r->i_cnt && r->i_edges && r->i_lout &&
-         r->i_cout && hipHostMalloc((void **)&r->h_cnt, 16, hipHostMallocDefault) == hipSuccess &&
-         hipEventCreateWithFlags(&r->ev_ielig, hipEventDisableTiming) == hipSuccess;
-    if (r->i_was) (void)hipMemsetAsync(r->i_was, 0, n, r->stream);
-    if (r->i_win) (void)hipMemsetAsync(r->i_win, 0, 2 * n, r->stream);
-  }
-  // the rounds' counts (the lookahead's EPZS rounds at every speed, the MV-
-  // stack rounds at speed 10): a device ring of count pairs + the ticket, the
-  // host-mapped publication ring
-  ok = ok && round_ring_alloc(r, r->rr, r->stream);
-  // speed 10: rav1e's MV stacks in coding-order rounds
-  r->exact = !r->s6 && !(cfg->flags & RV_REPLAY_MVREF_STANDIN);
-  if (r->exact) {
-    const size_t n = (size_t)g.nsb;
-    r->stk = (MvStack *)dalloc(r, n * sizeof(MvStack));
-    for (int l = 0; l < 3; l++) {
-      r->dec_lv[l] = (BlkDec *)dalloc(r, n * sizeof(BlkDec));
-      if (r->dec_lv[l]) (void)hipMemsetAsync(r->dec_lv[l], 0, n * sizeof(BlkDec), r->stream);
-      ok = ok && r->dec_lv[l];
-    }
-    r->mv_active = (uint8_t *)dalloc(r, n);
-    r->mv_list = (int32_t *)dalloc(r, 2 * n * 4);
-    ok = ok && r->stk && r->mv_active && r->mv_list;
-    // does a superblock's top-right neighbour (same tile) lie past the right
-    // frame edge, i.e. is it a must_split leaf?
-    for (int sb = 0; sb < g.nsb && r->lvl; sb++) {
-      const int fsx = g.tx0 + sb % g.tw, fsy = g.ty0 + sb / g.tw;
-      const int t0x = fsx - fsx % g.tws;
-      const int cols = std::min(g.tws * 16, g.w_in_b - t0x * 16);
-      if ((fsx + 1) * 64 <= g.W && (fsy + 1) * 64 <= g.H && fsy % g.ths != 0 &&
-          (fsx - t0x) * 16 + 16 < cols && (fsx + 2) * 64 > g.W)
-        r->edge_tr = true;
-    }
-  }
-  if (cfg->flags & RV_REPLAY_CDEF) {
-    if (!(cfg->flags & RV_REPLAY_DEBLOCK) || (g.W & 7) || (g.H & 7)) {
-      rv_set_error(RV_EINVAL, "rv_replay_create: RV_REPLAY_CDEF needs RV_REPLAY_DEBLOCK and a "
-                              "frame size that is a multiple of 8");
-      rv_replay_destroy(r);
-      return nullptr;
-    }
-    r->cdef = true;
-    const size_t n8 = (size_t)(g.W / 8) * (g.H / 8), n64 = (size_t)((g.W + 63) / 64) * ((g.H + 63) / 64);
-    r->cdef_dir = (uint8_t *)dalloc(r, n8);
-    r->cdef_var = (int32_t *)dalloc(r, n8 * 4);
-    r->cdef_idx = (uint8_t *)dalloc(r, n64);
-    ok = ok && r->cdef_dir && r->cdef_var && r->cdef_idx && alloc_input(r, r->cdef_pre, false);
-    if (r->cdef_idx) (void)hipMemsetAsync(r->cdef_idx, 0, n64, r->stream);
-  }
-  if (cfg->flags & RV_REPLAY_LRF) {
-    LrfGeo lg;
-    // (the unit size depends on the quantizer: rv_replay_set_level_params
-    // checks every level's; 100 here is the replay's default level 0)
-    if (!r->cdef || g.xdec != g.ydec ||
-        lrf_geometry(g.W, g.H, g.xdec, g.ydec, g.bd, 100, g.tws, g.ths, &lg) != RV_OK) {
-      rv_set_error(RV_EINVAL, "rv_replay_create: RV_REPLAY_LRF needs RV_REPLAY_CDEF, 4:2:0 or 4:4:4 "
-                              "(rav1e's enable_restoration is off in 4:2:2) and units of one superblock");
-      rv_replay_destroy(r);
-      return nullptr;
-    }
-    r->lrf = true;
-    r->lrf_err = (uint64_t *)dalloc(r, (size_t)3 * lg.nsb * 17 * 8);
-    r->lrf_xqd = (int8_t *)dalloc(r, (size_t)3 * lg.nsb * 32);
-    r->lrf_units = (int8_t *)dalloc(r, (size_t)3 * lg.nsb * 3);
-    ok = ok && r->lrf_err && r->lrf_xqd && r->lrf_units && alloc_input(r, r->lrf_out, false);
-    // RAV1E_LRF_FIX=0 (A/B): the one-wave serial decision; RAV1E_LRF_FIX_PASSES
-    // = 1 .. caps the fixed point's parallel passes (tests: the serial rest
-    // after the cap).  Read here, once: the worker threads of a pipelined
-    // replay must not call getenv per frame while the caller may setenv.
-    {
-      const char *fe = getenv("RAV1E_LRF_FIX"), *fp = getenv("RAV1E_LRF_FIX_PASSES");
-      r->lrf_fix_passes = (fe && fe[0] == '0') ? 0 : fp ? std::max(atoi(fp), 1) : 1 << 30;
-    }
-  }
-  r->entropy = (cfg->flags & RV_REPLAY_ENTROPY) != 0;
-  if (r->entropy && g.xdec != g.ydec) {
-    rv_set_error(RV_EINVAL, "rv_replay_create: RV_REPLAY_ENTROPY needs xdec == ydec");
-    rv_replay_destroy(r);
-    return nullptr;
-  }
-  if (cfg->flags & (RV_REPLAY_DEBLOCK | RV_REPLAY_ENTROPY)) {
-    r->deblock = (cfg->flags & RV_REPLAY_DEBLOCK) != 0;
-    r->mi_cols = (g.W + 3) / 4;
-    r->mi_rows = (g.H + 3) / 4;
-    r->mi_stride = (r->mi_cols + 15) / 16 * 16;
-    const size_t mb = (size_t)r->mi_stride * (r->mi_rows + 16);
-    r->mi_lg = (uint8_t *)dalloc(r, mb);
-    r->mi_skip = (uint8_t *)dalloc(r, mb);
-    ok = ok && r->mi_lg && r->mi_skip;
-    if (r->mi_lg) (void)hipMemsetAsync(r->mi_lg, 4, mb, r->stream);
-    if (r->mi_skip) (void)hipMemsetAsync(r->mi_skip, 0, mb, r->stream);
-    if (r->s6 && r->deblock) {
-      r->db_tally = (int64_t *)dalloc(r, 3 * 130 * 8);
-      r->db_dlev = (uint8_t *)dalloc(r, 4);
-      ok = ok && r->db_tally && r->db_dlev;
-    }
-  }
-  if (r->entropy) {  // F8 buffers, the host-mapped token rings and the coder thread
-    EcFrameBufs &b = r->ecb;
-    b.ntiles = ((g.tw + g.tws - 1) / g.tws) * ((g.th + g.ths - 1) / g.ths);
-    b.max_jobs = ec_max_jobs(g.nsb, b.ntiles);
-    b.map_w4 = g.tws * 16;
-    b.map_h4 = g.ths * 16;
-    b.jobs = (rv_ec_job *)dalloc(r, (size_t)b.max_jobs * sizeof(rv_ec_job));
-    b.sb_off = (uint32_t *)dalloc(r, ((size_t)g.nsb + 1) * 4);
-    b.map = (uint8_t *)dalloc(r, (size_t)b.ntiles * 3 * b.map_w4 * b.map_h4);
-    b.scratch = dalloc(r, rv_ec_scratch_bytes(b.max_jobs));
-    b.offsets = (uint32_t *)dalloc(r, ((size_t)b.max_jobs + 1) * 4);
-    b.dstat = (uint32_t *)dalloc(r, 16);
-    // one token per coded coefficient plus 4 per job covers every block
-    // whose levels stay below 3; more sets the overflow flag (an error)
-    b.cap = (uint32_t)((size_t)g.nsb * (1024 + 2 * r->ntx_c * 1024) + (size_t)b.max_jobs * 4);
-    ok = ok && b.jobs && b.sb_off && b.map && b.scratch && b.offsets && b.dstat;
-    EcHost *eh = new EcHost();
-    r->ech = eh;
-    eh->ntiles = b.ntiles;
-    for (int k = 0; k < 2 && ok; k++) {
-      ok = hipHostMalloc((void **)&eh->tok_h[k], (size_t)b.cap * 4,
-                         hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
-           hipHostMalloc((void **)&eh->stat_h[k], ((size_t)b.ntiles + 8) * 4,
-                         hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
-           // blocking sync: the coder thread sleeps instead of spinning on the GPU
-           hipEventCreateWithFlags(&eh->ev[k], hipEventBlockingSync | hipEventDisableTiming) ==
-               hipSuccess;
-    }
-    if (ok) eh->th = std::thread([eh] { eh->run(); });
-  }
   r->imp_bx = g.vis_w / 8;
   r->imp_by = g.vis_h / 8;
   r->n_imp = r->imp_bx * r->imp_by;
-  r->tail = (unsigned long long *)dalloc(r, 5 * 8);
-  ok = ok && r->coarse && r->half && r->look && r->half_l && r->la_list && r->full && r->sub &&
-       r->l_out && r->c_out && r->win &&
-       r->cand_list && r->cand_count && r->f4_args && r->cand_evals &&
-       r->l_lev && r->c_lev && r->words && r->tail;
-  if (ok) {
-    ok = hipMemsetAsync(r->words, 0, r->nwords * 8, r->stream) == hipSuccess &&
-         hipMemsetAsync(r->tail, 0, 5 * 8, r->stream) == hipSuccess &&
-         hipMemsetAsync(r->l_lev, 0, (size_t)g.nsb * 1024 * 4, r->stream) == hipSuccess &&
-         hipMemsetAsync(r->c_lev, 0, (size_t)g.nsb * r->ntx_c * 1024 * 4 * 2, r->stream) ==
-             hipSuccess;
+  const int32_t me[4] = {g.tx0, g.ty0, g.tw, g.th};
+  memcpy(r->grects, me, sizeof(me));
+  RV_R(configure_levels(r));
+  return configure_stages(r);
+}
+
+// the DPB and the inputs (a twin borrows the primary's)
+static void alloc_dpb(rv_replay *r, const rv_replay *share) {
+  r->slots = share ? share->slots : std::vector<RvSlot>(kSlots);
+  r->inputs = share ? share->inputs : std::vector<RvInput>(r->cfg.n_inputs);
+  if (share) return;
+  for (auto &s : r->slots) alloc_slot(r, s);
+  for (auto &in : r->inputs) alloc_input(r, in, true);
+}
+
+// the 64x64 stages: F1 .. F3 and the lookahead (results per superblock and
+// reference), F4 / F6, the result words and their tail
+static void alloc_superblocks(rv_replay *r) {
+  const Geo &g = r->g;
+  const size_t nsb = (size_t)g.nsb, nr = nsb * g.R, nc = nsb * g.C;
+  r->coarse = r->dev<rv_fs_result>(nr);
+  r->half = r->dev<rv_fs_result>(nr * 4);
+  r->look = r->dev<rv_fs_result>(nr * 16, Fill::Zero);
+  r->half_l = r->dev<rv_fs_result>(nr * 4, Fill::Zero);
+  r->la_list = r->dev<int32_t>(nr * 20);
+  r->full = r->dev<rv_fs_result>(nr);
+  r->sub = r->dev<rv_fs_result>(nr);
+  r->ds_evals = r->dev<uint32_t>((size_t)rv_replay::kRing * 2 * nr, Fill::Zero);
+  r->l_out = r->dev<uint64_t>(nc * 3);
+  r->c_out = r->dev<uint64_t>(nc * r->ntx_c * 3 * 2);
+  r->win = r->dev<RdoWinner>(nsb);
+  r->cand_list = r->dev<int32_t>(nc);
+  // zeroed: tag 0 matches no frame
+  r->cand_key = r->dev<CandKey>(nsb * (g.R * g.M + kCompModes), Fill::Zero);
+  r->f3dirty = r->dev<uint8_t>(nsb * g.R);
+  r->f2dirty = r->dev<uint8_t>(nsb * g.R * 4);
+  r->cand_count = r->dev<int32_t>(2, Fill::Zero);  // [single, compound]
+  r->f4_args = r->dev<RdoArgs>(4);
+  r->cand_evals = r->dev<uint32_t>((size_t)rv_replay::kRing * 2 * kLevels, Fill::Zero);
+  r->l_lev = r->dev<int32_t>(nsb * 1024, Fill::Zero);
+  r->c_lev = r->dev<int32_t>(nsb * r->ntx_c * 1024 * 2, Fill::Zero);
+  r->words = r->dev<uint64_t>(r->nwords, Fill::Zero);
+  r->tail = r->dev<unsigned long long>(5, Fill::Zero);
+}
+
+// the 32x32 .. 8x8 levels' arrays and every level's leaf list
+static void alloc_levels(rv_replay *r) {
+  if (!r->lvl) return;
+  size_t nleaf = (size_t)r->g.nsb;
+  for (int l = 1; l < kLevels; l++) {
+    rv_replay::PLevel &P = r->pl[l];
+    const size_t n = (size_t)P.n, nr = n * r->g.R, nc = n * r->g.C;
+    P.full = r->dev<rv_fs_result>(nr);
+    P.sub = r->dev<rv_fs_result>(nr);
+    P.l_out = r->dev<uint64_t>(nc * 3);
+    P.c_out = r->dev<uint64_t>(nc * 3 * 2);
+    P.win = r->dev<RdoWinner>(n);
+    P.cand_list = r->dev<int32_t>(nc);
+    P.cand_count = r->dev<int32_t>(2, Fill::Zero);
+    P.l_lev = r->dev<int32_t>(n * P.B * P.B, Fill::Zero);
+    P.c_lev = r->dev<int32_t>(n * P.bc * P.bch * 2, Fill::Zero);
+    nleaf += n;
   }
+  int32_t *lf = r->dev<int32_t>(nleaf);
+  r->leaf_count = r->dev<int32_t>(kLevels, Fill::Zero);
+  for (int l = 0; l < kLevels && lf; l++) {
+    r->pl[l].leaf = lf;
+    lf += r->pl[l].n;
+  }
+}
+
+static void alloc_intra(rv_replay *r) {
+  r->i_stats = r->dev<uint32_t>((size_t)rv_replay::kRing * 3, Fill::Zero);
+  if (!r->intra) return;
+  const size_t n = (size_t)r->g.nsb;
+  r->i_elig = r->dev<uint8_t>(n);
+  r->i_was = r->dev<uint8_t>(n, Fill::Zero);
+  r->i_win = r->dev<uint8_t>(2 * n, Fill::Zero);
+  r->i_modes = r->dev<uint8_t>(4 * n);
+  for (int32_t **list : {&r->i_mark, &r->i_list[0], &r->i_list[1], &r->i_commit, &r->i_revert})
+    *list = r->dev<int32_t>(n);
+  r->i_cnt = r->dev<int32_t>(4);
+  r->i_edges = r->dev<uint8_t>(n * 3 * kIntraEdge * (r->g.hbd ? 2 : 1));
+  r->i_lout = r->dev<uint64_t>(n * 3 * 3);
+  r->i_cout = r->dev<uint64_t>(n * 6 * 3 * 2);
+  r->h_cnt = r->own.pinned<int32_t>(4, hipHostMallocDefault);
+  r->ev_ielig = r->own.event(hipEventDisableTiming);
+}
+
+// the rounds' counts (the lookahead's EPZS rounds at every speed, the MV-
+// stack rounds at speed 10) and the stacks' state
+static void alloc_mvref(rv_replay *r) {
+  round_ring_alloc(r->own, r->own, r->rr, r->stream);
+  if (!r->exact) return;
+  const size_t n = (size_t)r->g.nsb;
+  r->stk = r->dev<MvStack>(n);
+  for (int l = 0; l < 3; l++) r->dec_lv[l] = r->dev<BlkDec>(n, Fill::Zero);
+  r->mv_active = r->dev<uint8_t>(n);
+  r->mv_list = r->dev<int32_t>(2 * n);
+}
+
+// the loop filters: CDEF, loop restoration, the block map, speed 6's tallies
+static void alloc_filters(rv_replay *r) {
+  const Geo &g = r->g;
+  const size_t n8 = (size_t)(g.W / 8) * (g.H / 8), n64 = (size_t)((g.W + 63) / 64) * ((g.H + 63) / 64);
+  if (r->cdef) {
+    r->cdef_dir = r->dev<uint8_t>(n8);
+    r->cdef_var = r->dev<int32_t>(n8);
+    r->cdef_idx = r->dev<uint8_t>(n64, Fill::Zero);
+    alloc_input(r, r->cdef_pre, false);
+  }
+  if (r->lrf) {  // per plane and superblock of the frame (LrfGeo::nsb)
+    r->lrf_err = r->dev<uint64_t>(3 * n64 * 17);
+    r->lrf_xqd = r->dev<int8_t>(3 * n64 * 32);
+    r->lrf_units = r->dev<int8_t>(3 * n64 * 3);
+    alloc_input(r, r->lrf_out, false);
+  }
+  if (!r->deblock && !r->entropy) return;
+  const size_t mb = (size_t)r->mi_stride * (r->mi_rows + 16);
+  r->mi_lg = r->dev<uint8_t>(mb, Byte(4));
+  r->mi_skip = r->dev<uint8_t>(mb, Fill::Zero);
+  if (r->s6 && r->deblock) {
+    r->db_tally = r->dev<int64_t>(3 * 130);
+    r->db_dlev = r->dev<uint8_t>(4);
+  }
+}
+
+// the timing event ring; speed 10: the edge levels' stream and its events
+static void alloc_sync(rv_replay *r) {
   for (int f = 0; f < rv_replay::kRing; f++)
-    for (int i = 0; i < kEvCount; i++)
-      ok = ok && hipEventCreateWithFlags(&r->evs[f][i], hipEventDisableSystemFence) == hipSuccess;
-  {
-    const char *e = getenv("RAV1E_HIP_REPLAY_SERIAL");
-    r->overlap = !(e && e[0] == '1');
+    for (int i = 0; i < kEvCount; i++) r->evs[f][i] = r->own.event(hipEventDisableSystemFence);
+  if (!r->overlap || !r->lvl || r->s6) return;
+  for (hipEvent_t *ev : {&r->ev_efork, &r->ev_l1me, &r->ev_epart})
+    *ev = r->own.event(hipEventDisableTiming);
+  // one stream for all levels (in order): every stream beyond the hardware
+  // queues (GPU_MAX_HW_QUEUES) is multiplexed onto them
+  const hipStream_t es = r->own.stream();
+  for (int l = 1; l < kLevels; l++) {
+    r->edge[l] = es;
+    r->ev_ejoin[l] = r->own.event(hipEventDisableTiming);
+    r->ev_ecommit[l] = r->own.event(hipEventDisableTiming);
   }
-  if (r->overlap && r->lvl && !r->s6) {
-    ok = ok && hipEventCreateWithFlags(&r->ev_efork, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&r->ev_l1me, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&r->ev_epart, hipEventDisableTiming) == hipSuccess;
-    // one stream for all levels (in order): every stream beyond the hardware
-    // queues (GPU_MAX_HW_QUEUES) is multiplexed onto them
-    ok = ok && hipStreamCreateWithFlags(&r->edge[1], hipStreamNonBlocking) == hipSuccess;
-    for (int l = 1; l < kLevels; l++) {
-      r->edge[l] = r->edge[1];
-      ok = ok && hipEventCreateWithFlags(&r->ev_ejoin[l], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&r->ev_ecommit[l], hipEventDisableTiming) == hipSuccess;
+}
+
+// F8: its buffers, the host-mapped token rings, then the coder thread (the
+// last thing created, and only if nothing has failed)
+static void alloc_entropy(rv_replay *r) {
+  if (!r->entropy) return;
+  EcFrameBufs &b = r->ecb;
+  b.jobs = r->dev<rv_ec_job>((size_t)b.max_jobs);
+  b.sb_off = r->dev<uint32_t>((size_t)r->g.nsb + 1);
+  b.map = r->dev<uint8_t>((size_t)b.ntiles * 3 * b.map_w4 * b.map_h4);
+  b.scratch = r->dev<uint8_t>(rv_ec_scratch_bytes(b.max_jobs));
+  b.offsets = r->dev<uint32_t>((size_t)b.max_jobs + 1);
+  b.dstat = r->dev<uint32_t>(4);
+  EcHost *eh = r->ech = new EcHost();
+  eh->ntiles = b.ntiles;
+  for (int k = 0; k < 2; k++) {
+    eh->tok_h[k] = r->own.pinned<uint32_t>(b.cap, hipHostMallocMapped | hipHostMallocCoherent);
+    eh->stat_h[k] = r->own.pinned<uint32_t>((size_t)b.ntiles + 8, hipHostMallocMapped | hipHostMallocCoherent);
+    // blocking sync: the coder thread sleeps instead of spinning on the GPU
+    eh->ev[k] = r->own.event(hipEventBlockingSync | hipEventDisableTiming);
+  }
+  if (!r->own.failed) eh->th = std::thread([eh] { eh->run(); });
+}
+
+}  // namespace rv
+
+extern "C" {
+
+void rv_replay_destroy(rv_replay *r) {
+  if (!r) return;
+  la_engine_destroy(r);  // its thread first: it launches on the replay's arrays
+  // the streams drain before anything they may still read is freed
+  if (r->stream) (void)hipStreamSynchronize(r->stream);
+  if (r->ech) {  // the host coder finishes the frames it holds, then stops
+    {
+      std::lock_guard<std::mutex> lk(r->ech->mu);
+      r->ech->stop = true;
     }
+    r->ech->cv.notify_all();
+    if (r->ech->th.joinable()) r->ech->th.join();
+    delete r->ech;
   }
-  const size_t ev_bytes = (size_t)rv_replay::kRing * 2 * nr * 4;
-  r->ds_evals = (uint32_t *)dalloc(r, ev_bytes);
-  ok = ok && r->ds_evals && hipMemsetAsync(r->ds_evals, 0, ev_bytes, r->stream) == hipSuccess;
-  r->grects[0] = g.tx0;
-  r->grects[1] = g.ty0;
-  r->grects[2] = g.tw;
-  r->grects[3] = g.th;
-  for (int lv = 0; lv < 3; lv++)
-    r->jobs_half[lv] = r->jobs_full[lv] = r->jobs_sub[lv] = r->jobs_look[lv] = nullptr;
-  if (!ok) {
-    rv_set_error(RV_EHIP, "rv_replay_create: device allocation failed");
-    rv_replay_destroy(r);
+  if (r->edge[1]) (void)hipStreamSynchronize(r->edge[1]);
+  r->own.release();
+  delete r;
+}
+
+// share: a primary instance whose DPB and inputs this one borrows
+// (rv_replay_create_twin)
+static rv_replay *create_impl(const rv_replay_cfg *cfg, void *stream, const rv_replay *share) {
+  rv_replay *r = new rv_replay();
+  if (replay_configure(cfg, r) != RV_OK) {
+    delete r;
     return nullptr;
   }
-  if (hipStreamSynchronize(r->stream) != hipSuccess) {
+  r->own_stream = !stream;
+  r->stream = stream ? (hipStream_t)stream : r->own.stream();
+  if (!r->stream) {
+    rv_set_error(RV_EHIP, "rv_replay_create: stream");
+    delete r;
+    return nullptr;
+  }
+  alloc_dpb(r, share);
+  alloc_superblocks(r);
+  alloc_levels(r);
+  alloc_intra(r);
+  alloc_mvref(r);
+  alloc_filters(r);
+  alloc_sync(r);
+  alloc_entropy(r);
+  if (r->own.failed) rv_set_error(RV_EHIP, "rv_replay_create: device allocation failed");
+  if (r->own.failed || hipStreamSynchronize(r->stream) != hipSuccess) {
     rv_replay_destroy(r);
     return nullptr;
   }
   return r;
 }
 
-// The quantizers and lambdas of the frames of pyramid level `level`
-// (FrameInvariants::set_quantizers, src/encoder.rs:865-880, from
-// QuantizerParameters; the host computes them, rav1e_amd/rate.py).  Every
-// level must be set before the first inter frame.
 rv_replay *rv_replay_create(const rv_replay_cfg *cfg, void *stream) {
   return create_impl(cfg, stream, nullptr);
 }
@@ -1243,6 +1174,10 @@ int rv_replay_seek(rv_replay *r, long n) {
 
 void *rv_replay_stream(rv_replay *r) { return r ? (void *)r->stream : nullptr; }
 
+// The quantizers and lambdas of the frames of pyramid level `level`
+// (FrameInvariants::set_quantizers, src/encoder.rs:865-880, from
+// QuantizerParameters; the host computes them, rav1e_amd/rate.py).  Every
+// level must be set before the first inter frame.
 int rv_replay_set_level_params(rv_replay *r, int level, const rv_replay_level_params *p) {
   if (!r || !p || level < 0 || level > 2 || p->base_q_idx < 1 || p->base_q_idx > 255)
     return rv_set_error(RV_EINVAL, "rv_replay_set_level_params: bad arguments");
@@ -1350,7 +1285,9 @@ int rv_replay_set_importances(rv_replay *r, const float *host, int n) {
     return RV_OK;
   }
   if (n != need) return rv_set_error(RV_EINVAL, "rv_replay_set_importances: size != w_imp * h_imp");
-  float *d = (float *)dalloc(r, (size_t)need * 4);
+  // A fresh buffer per call, all kept until destroy (on purpose): frames in
+  // flight on the non-blocking stream may still read the previous one.
+  float *d = r->dev<float>((size_t)need);
   if (!d) return rv_set_error(RV_EHIP, "rv_replay_set_importances: alloc");
   RV_H(hipMemcpy(d, host, (size_t)need * 4, hipMemcpyHostToDevice));
   r->imp = d;
@@ -1383,8 +1320,8 @@ int rv_replay_set_groups(rv_replay *r, int n_groups, const int32_t *rects, int m
   }
   r->xbytes = (most + 255) / 256 * 256;
   if (n_groups > 1 || comm) {  // one group + a communicator: a 1-rank all-gather
-    r->xsend = (uint8_t *)dalloc(r, r->xbytes);
-    r->xrecv = (uint8_t *)dalloc(r, r->xbytes * n_groups);
+    r->xsend = r->dev<uint8_t>(r->xbytes);
+    r->xrecv = r->dev<uint8_t>(r->xbytes * n_groups);
     if (!r->xsend || !r->xrecv) return rv_set_error(RV_EHIP, "rv_replay_set_groups: alloc");
   }
   r->comm = comm;
@@ -1548,10 +1485,10 @@ int rv_replay_set_kernel_probe(rv_replay *r, int on) {
   if (on && r->kp_ev[0].empty()) {
     for (int p = 0; p < P; p++) {
       r->kp_ev[p].assign(2 * rv_replay::kKp, nullptr);
-      for (auto &ev : r->kp_ev[p]) RV_H(hipEventCreate(&ev));
-      r->kp_cnt[p] = (uint32_t *)dalloc(r, C * sizeof(uint32_t));
-      r->kp_ts[p] = (unsigned long long *)dalloc(r, 2 * sizeof(unsigned long long) * rv_replay::kKp);
-      if (!r->kp_cnt[p] || !r->kp_ts[p])
+      for (auto &ev : r->kp_ev[p]) ev = r->own.event(hipEventDefault);
+      r->kp_cnt[p] = r->dev<uint32_t>(C);
+      r->kp_ts[p] = r->dev<unsigned long long>(2 * rv_replay::kKp);
+      if (r->own.failed)
         return rv_set_error(RV_EHIP, "rv_replay_set_kernel_probe: allocation failed");
     }
     int dev = 0, khz = 0;

@@ -362,12 +362,6 @@ static int la_step(rv_replay *r, long m) {
   return RV_OK;
 }
 
-// the engine's stream
-static int la_stream_create(RvLaEngine *E) {
-  RV_H(hipStreamCreateWithFlags(&E->las, hipStreamNonBlocking));
-  return RV_OK;
-}
-
 static void la_thread_main(rv_replay *r) {
   RvLaEngine &E = *r->eng;
   (void)hipSetDevice(E.dev);
@@ -389,7 +383,8 @@ static void la_thread_main(rv_replay *r) {
       });
       if (E.stop) return;
     }
-    int rc = E.las ? RV_OK : la_stream_create(&E);
+    if (!E.las) E.las = E.own.stream();
+    int rc = E.las ? RV_OK : rv_set_error(RV_EHIP, "the lookahead engine's stream");
     if (rc == RV_OK) rc = ensure_jobs(r);  // (the engine may start before the first frame)
     if (rc == RV_OK) rc = la_step(r, m);
     if (rc != RV_OK) {
@@ -404,23 +399,19 @@ static void la_thread_main(rv_replay *r) {
 
 void la_engine_destroy(rv_replay *r) {
   RvLaEngine *E = r->eng;
-  r->eng = nullptr;
-  if (!E || !r->eng_owned) return;
-  {
-    std::lock_guard<std::mutex> lk(E->mu);
-    E->stop = true;
-    E->cv.notify_all();
+  if (E && r->eng_owned) {
+    {
+      std::lock_guard<std::mutex> lk(E->mu);
+      E->stop = true;
+      E->cv.notify_all();
+    }
+    // (its thread reads r->eng from its first statement on: cleared once it has ended)
+    if (E->th.joinable()) E->th.join();
+    if (E->las) (void)hipStreamSynchronize(E->las);
+    E->own.release();
+    delete E;  // its device arrays are the replay's allocations (freed with it)
   }
-  if (E->th.joinable()) E->th.join();
-  if (E->las) (void)hipStreamSynchronize(E->las);
-  for (auto &en : E->ring)
-    for (hipEvent_t ev : {en.ev_imp, en.ev_used, en.ev_data, en.ev_xchg})
-      if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : E->hub_ev)
-    if (ev) (void)hipEventDestroy(ev);
-  if (E->rr.h_pub) (void)hipHostFree(E->rr.h_pub);
-  if (E->las) (void)hipStreamDestroy(E->las);
-  delete E;  // its device arrays are the replay's allocations (freed with it)
+  r->eng = nullptr;
 }
 
 // Tile groups over RCCL: before frame n takes its importances, the encode
@@ -554,7 +545,6 @@ int rv_replay_set_imp_window(rv_replay *r, int window, long limit) {
     return rv_set_error(RV_EINVAL, "rv_replay_set_imp_window: bad arguments");
   if (r->coded > 0) return rv_set_error(RV_EINVAL, "rv_replay_set_imp_window: after the first frame");
   const Geo &g = r->g;
-  (void)g;  // a tile group's window exchanges parts (rv_replay_set_la_exchange)
   if (r->eng && !r->eng_owned)
     return rv_set_error(RV_EINVAL, "rv_replay_set_imp_window: on the primary instance");
   la_engine_destroy(r);
@@ -568,23 +558,23 @@ int rv_replay_set_imp_window(rv_replay *r, int window, long limit) {
   // least-used hardware queue, so the engine's then shares one with a
   // frame-edge or entropy stream instead of with the twin's round kernels
   // (which the trace showed waiting 6-7 us behind the lookahead's).
-  bool ok = hipGetDevice(&E->dev) == hipSuccess && round_ring_alloc(r, E->rr, r->stream);
+  // Its device arrays are the replay's (freed with it, after the encode
+  // stream has drained); the rest is its own.
+  E->own.failed = hipGetDevice(&E->dev) != hipSuccess;
+  round_ring_alloc(r->own, E->own, E->rr, r->stream);
   const int ni = g.w_imp * g.h_imp, nr = g.nsb * r->RA;  // the lookahead's references
-  E->la_list = ok ? (int32_t *)dalloc(r, (size_t)nr * 20 * 4) : nullptr;
+  E->la_list = r->dev<int32_t>((size_t)nr * 20);
   E->scratch_bytes = impwin_scratch_bytes(ni);
-  E->scratch = ok ? dalloc(r, E->scratch_bytes) : nullptr;
-  ok = ok && E->la_list && E->scratch;
+  E->scratch = r->dev<uint8_t>(E->scratch_bytes);
   E->ring.resize((size_t)E->RW);
   const size_t ob = ((size_t)nr * 21 * sizeof(rv_fs_result) + 255) / 256 * 256;
   for (auto &en : E->ring) {
-    if (!ok) break;
-    uint8_t *m = (uint8_t *)dalloc(r, ob + impwin_frame_bytes(ni, r->RA));
-    ok = m && hipMemsetAsync(m, 0, ob, r->stream) == hipSuccess &&
-         hipEventCreateWithFlags(&en.ev_imp, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&en.ev_used, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&en.ev_data, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&en.ev_xchg, hipEventDisableTiming) == hipSuccess;
-    if (!ok) break;
+    // one block per entry: the lookahead's results (zeroed), then the ImpFrame
+    uint8_t *m = r->dev<uint8_t>(ob + impwin_frame_bytes(ni, r->RA));
+    if (!m || hipMemsetAsync(m, 0, ob, r->stream) != hipSuccess) E->own.failed = true;
+    if (r->own.failed || E->own.failed) break;
+    for (hipEvent_t *ev : {&en.ev_imp, &en.ev_used, &en.ev_data, &en.ev_xchg})
+      *ev = E->own.event(hipEventDisableTiming);
     en.o.coarse = (rv_fs_result *)m;
     en.o.half_l = en.o.coarse + nr;
     en.o.look = en.o.half_l + (size_t)nr * 4;
@@ -593,7 +583,7 @@ int rv_replay_set_imp_window(rv_replay *r, int window, long limit) {
   E->pyr_display.assign(r->inputs.size(), -1);
   r->eng = E;
   r->eng_owned = true;
-  if (!ok || hipStreamSynchronize(r->stream) != hipSuccess) {
+  if (r->own.failed || E->own.failed || hipStreamSynchronize(r->stream) != hipSuccess) {
     la_engine_destroy(r);
     return rv_set_error(RV_EHIP, "rv_replay_set_imp_window: allocation failed");
   }
@@ -638,8 +628,8 @@ int rv_replay_set_la_exchange(rv_replay *r, void *comm, rv_la_hub *hub) {
   }
   E.pbytes = (most + 255) / 256 * 256;
   if (comm) {
-    E.psend = (uint8_t *)dalloc(r, E.pbytes);
-    E.precv = (uint8_t *)dalloc(r, E.pbytes * (size_t)r->n_groups);
+    E.psend = r->dev<uint8_t>(E.pbytes);
+    E.precv = r->dev<uint8_t>(E.pbytes * (size_t)r->n_groups);
     if (!E.psend || !E.precv) return rv_set_error(RV_EHIP, "rv_replay_set_la_exchange: alloc");
     E.comm = comm;
     return RV_OK;
@@ -650,12 +640,10 @@ int rv_replay_set_la_exchange(rv_replay *r, void *comm, rv_la_hub *hub) {
   std::lock_guard<std::mutex> lk(hub->mu);
   for (int s = 0; s < rv_la_hub::kRing; s++) {
     if (hub->buf[s][k]) return rv_set_error(RV_EINVAL, "rv_replay_set_la_exchange: group joined twice");
-    hub->buf[s][k] = (uint8_t *)dalloc(r, E.pbytes);
-    hipEvent_t ev = nullptr;
-    RV_H(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    E.hub_ev.push_back(ev);
-    hub->ev[s][k] = ev;
-    if (!hub->buf[s][k]) return rv_set_error(RV_EHIP, "rv_replay_set_la_exchange: alloc");
+    hub->buf[s][k] = r->dev<uint8_t>(E.pbytes);
+    hub->ev[s][k] = E.own.event(hipEventDisableTiming);  // (released with the engine)
+    if (!hub->buf[s][k] || !hub->ev[s][k])
+      return rv_set_error(RV_EHIP, "rv_replay_set_la_exchange: alloc");
   }
   E.hub = hub;
   E.hub_k = k;

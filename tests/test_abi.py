@@ -79,6 +79,46 @@ def test_argument_validation_rejects_without_launch():
     assert L.rv_sad_batch(C.byref(p), C.byref(p), None, 0, 8, 8, out, None) == R.RV_OK
 
 
+_DEBLOCK, _CDEF, _LRF, _ENTROPY, _SPEED6 = 16, 32, 512, 128, 8  # RV_REPLAY_* (rav1e_hip.h)
+
+
+@pytest.mark.parametrize("change,text", [
+    (dict(width=0), "bad config"),
+    (dict(width=68), "bad config"),
+    (dict(bit_depth=9), "bad config"),
+    (dict(n_refs=3), "bad config"),
+    (dict(n_inputs=0), "bad config"),
+    (dict(tile_x0=1, tile_w=2), "not a rectangle of whole tiles"),
+    (dict(tile_w_sb=2, tile_x0=1, tile_w=1), "not a rectangle of whole tiles"),
+    (dict(flags=_SPEED6, xdec=1, ydec=0), "speed 6 needs"),
+    (dict(flags=_CDEF), "RV_REPLAY_CDEF needs"),
+    (dict(flags=_DEBLOCK | _LRF), "RV_REPLAY_LRF needs"),
+    (dict(flags=_DEBLOCK | _CDEF | _LRF, xdec=1, ydec=0), "RV_REPLAY_LRF needs"),
+    (dict(flags=_ENTROPY, xdec=1, ydec=0), "RV_REPLAY_ENTROPY needs"),
+    (dict(flags=_SPEED6 | _CDEF, xdec=1, ydec=0), "speed 6 needs"),  # two faults: the first one
+], ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()) if isinstance(v, dict) else None)
+def test_replay_create_rejects_before_any_device_call(change, text):
+    """rv_replay_create checks the whole configuration on the host
+    (replay_configure) before it creates a stream or allocates: every bad
+    configuration returns NULL with its own message -- the first fault's, in
+    the order the checks are written -- and never a stream or allocation
+    error, with or without a device."""
+    from rav1e_amd import replay as RP
+    assert (_DEBLOCK, _CDEF, _LRF, _ENTROPY, _SPEED6) == (
+        RP.RV_REPLAY_DEBLOCK, RP.RV_REPLAY_CDEF, RP.RV_REPLAY_LRF, RP.RV_REPLAY_ENTROPY,
+        RP.RV_REPLAY_SPEED6)
+    cfg = R.RvReplayCfg()
+    cfg.width, cfg.height, cfg.xdec, cfg.ydec, cfg.bit_depth = 128, 128, 1, 1, 8
+    cfg.n_refs, cfg.n_inputs = 2, 4
+    for k, v in change.items():
+        setattr(cfg, k, v)
+    L = R.lib()
+    assert not L.rv_replay_create(C.byref(cfg), None)
+    err = L.rv_last_error().decode()
+    assert text in err, err
+    assert "stream" not in err and "allocation" not in err, err
+
+
 def test_python_mirror_enums_follow_reference_order():
     assert R.BlockSize.from_width_and_height(64, 16) == R.BlockSize.BLOCK_64X16 == 21
     assert R.TxSize.TX_64X16 == 18 and R.TxSize(4).width() == 64

@@ -547,6 +547,31 @@ def test_gpu_replay_matches_cpu_replay(w, h, xdec, ydec, bd, refs, tiling, flags
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(136, 72), (128, 128)])  # with / without frame-edge superblocks
+@pytest.mark.parametrize("flags", [
+    0, RP.RV_REPLAY_SPEED6, RP.RV_REPLAY_DEBLOCK | RP.RV_REPLAY_CDEF, _LRF,
+    _LRF | RP.RV_REPLAY_SPEED6, RP.RV_REPLAY_ENTROPY | RP.RV_REPLAY_DEBLOCK,
+    RP.RV_REPLAY_MVREF_STANDIN, RP.RV_REPLAY_NO_INTRA])
+def test_gpu_replay_lifecycle(w, h, flags):
+    """Everything an instance can own is created and released, no frame
+    coded: create (with the level params), the kernel probe's events and
+    arrays, an importance window's engine twice (the second replaces the
+    first), a twin, then the twin and the primary closed.  Every call
+    succeeds, and a fresh replay afterwards still equals the CPU replay."""
+    import rav1e_amd as R
+    R.require_device(0)
+    L = R.lib()
+    g = RP.HipReplay(w, h, flags=flags)
+    assert L.rv_replay_set_kernel_probe(g.h, 1) == R.RV_OK, L.rv_last_error()
+    assert L.rv_replay_set_imp_window(g.h, 3, 0) == R.RV_OK, L.rv_last_error()
+    assert L.rv_replay_set_imp_window(g.h, 5, 0) == R.RV_OK, L.rv_last_error()
+    t = g.twin()
+    t.close()
+    g.close()
+    _gpu_vs_cpu(128, 128, 1, 1, 8, 2, 2, None, flags)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("flags", [_LRF, _LRF | RP.RV_REPLAY_SPEED6])
 def test_gpu_replay_serial_mode(monkeypatch, flags):
     """RAV1E_HIP_REPLAY_SERIAL=1 (the profiling mode, read at create): the
