@@ -739,6 +739,101 @@ typedef struct rv_fs_result {
   uint64_t cost;
 } rv_fs_result;
 
+/* ---- MV reference stacks (src/context.rs:2308-2965) -----------------------
+ * ContextWriter::find_mvrefs / setup_mvref_list for blocks of any supported
+ * size over a tile's grid of 4x4-unit block records, as an operator: paint the
+ * grid from the blocks a tile committed, query it, or fill the stack fields
+ * (mode_context, num_mv_found, weight, ref_mv) that rv_ec_mode_tokenize and
+ * rv_ec_cand_tokenize read out of every rv_ec_mode_job.
+ *
+ * For the leaves of a final partition find_mvrefs never reads a cell coded at
+ * or after the querying block, so the stacks of every block of a painted grid
+ * are the ones the reference saw when it coded that block: one launch, no
+ * coding-order chain.
+ *
+ * rv_mv_blk: what the scans read of a Block.  ref: RefType codes (INTRA_FRAME
+ * 0 .. NONE_FRAME 8), n4_w / n4_h: the block's size in 4x4 units, newmv: its
+ * mode counts as a NEWMV one (add_ref_mv_candidate, :2389-2428).
+ * Block::default() (:1425-1442) is {ref {0, 0}, n4_w = n4_h = 16, zero MVs}:
+ * not zero-fill, the scans step by n4_w of blocks that are not inter.
+ * rv_mvref_tile: a tile's size (cols, rows <= grid_w, grid_h) and its origin
+ * in the frame, in 4x4 units.  rv_mvref_geom: n_tiles grids of grid_h rows of
+ * grid_w records each (tile t's cell (x, y) at (t * grid_h + y) * grid_w + x);
+ * frame_cols / frame_rows: the frame in 4x4 units (the MV clamp); sign_bias:
+ * bit r - 1 = ref_frame_sign_bias of RefType r (1..7).
+ * rv_mvref_query: block (bx, by) of bw4 x bh4 units in tile `tile`, stack of
+ * ref (ref[1] = NONE_FRAME: single reference).  rv_mvref_result: the value
+ * find_mvrefs returns, the stack's length and its entries (at most 8 from the
+ * scans, 3 after the extra search). */
+typedef struct rv_mv_blk {
+  int8_t ref[2];
+  uint8_t n4_w, n4_h, newmv, pad[3];
+  rv_mv mv[2];
+} rv_mv_blk;
+typedef struct rv_mv_cand {
+  rv_mv this_mv, comp_mv;
+  uint32_t weight;
+} rv_mv_cand;
+typedef struct rv_mvref_tile {
+  int32_t cols, rows, mi_x, mi_y;
+} rv_mvref_tile;
+typedef struct rv_mvref_geom {
+  int32_t n_tiles, grid_w, grid_h, frame_cols, frame_rows;
+  uint32_t sign_bias;
+} rv_mvref_geom;
+typedef struct rv_mvref_query {
+  int32_t tile, bx, by, bw4, bh4, ref[2], reserved;
+} rv_mvref_query;
+typedef struct rv_mvref_result {
+  int32_t mode_context, n;
+  rv_mv_cand stack[9];
+} rv_mvref_result;
+/* Shared by the three entry points: d_tiles geom.n_tiles records; d_grid
+ * n_tiles * grid_h * grid_w records, 16-byte aligned; d_status 1 u32 (cleared
+ * here): the rejected items, which write nothing and of which nothing is used
+ * as an index.  Before any HIP call: RV_EINVAL for a null pointer, n < 0 or
+ * > 2^22, n_tiles outside 1..1024, grid_w / grid_h not a multiple of 16,
+ * below 16 (the smallest tile, one superblock) or above 16384, more than 2^28
+ * cells in all, a misaligned d_grid, frame_cols / frame_rows outside 1..2^20,
+ * sign_bias above 7 bits.  A tile record
+ * the grid cannot hold (cols / rows outside 1..grid_w / grid_h, a negative
+ * origin) is found on the device: every item that names it is rejected.
+ *
+ * rv_mvref_grid_paint: every cell Block::default(), then each kind-0 job's
+ * bsize rectangle clipped to its tile's cols x rows, with the job's ref and mv
+ * and newmv from luma_mode; where jobs overlap the later one in the array
+ * wins.  Partition nodes paint nothing.  Rejected: a tile out of range,
+ * a position outside the tile, bsize above BLOCK_64X64 in either direction,
+ * refs outside 0..8, MVs outside int16.  d_scratch:
+ * rv_mvref_paint_scratch_bytes(geom) bytes.  n == 0 paints nothing and
+ * returns RV_OK without a launch.
+ *
+ * rv_find_mvrefs_batch: d_results[i] for query i.  Supported sizes: bw4, bh4
+ * in {2, 4, 8, 16}, square, 2:1 or 1:2, at a position that is a multiple of
+ * the size and inside the tile; ref[0] 0..7 (INTRA_FRAME: context 0, empty
+ * stack, as find_mvrefs), ref[1] 1..8.  Everything else is rejected and its
+ * d_results slot is left as it was.
+ *
+ * rv_ec_mode_fill_stacks: for every kind-0 job with an inter luma_mode
+ * (>= NEARESTMV) the query {ref[0], ref[1]} at the job's block against d_grid;
+ * mode_context, num_mv_found, weight[i] (0 from min(n, 4) on) and ref_mv
+ * (entry 0's this_mv, comp_mv; zero for an empty stack) are written into the
+ * job as encode_block_post_cdef reads them (src/encoder.rs:1531-1557).  Intra
+ * blocks and partition nodes are untouched, and so are rejected jobs.
+ * d_stacks: NULL, or n records; record i is written for the jobs that are
+ * filled.  The grid need not come from these jobs: a candidate list is filled
+ * against the committed blocks' grid. */
+size_t rv_mvref_paint_scratch_bytes(rv_mvref_geom geom);
+int rv_mvref_grid_paint(const rv_ec_mode_job *d_jobs, int n, rv_mvref_geom geom,
+                        const rv_mvref_tile *d_tiles, rv_mv_blk *d_grid, void *d_scratch,
+                        uint32_t *d_status, void *stream);
+int rv_find_mvrefs_batch(const rv_mvref_query *d_queries, int n, rv_mvref_geom geom,
+                         const rv_mvref_tile *d_tiles, const rv_mv_blk *d_grid,
+                         rv_mvref_result *d_results, uint32_t *d_status, void *stream);
+int rv_ec_mode_fill_stacks(rv_ec_mode_job *d_jobs, int n, rv_mvref_geom geom,
+                           const rv_mvref_tile *d_tiles, const rv_mv_blk *d_grid,
+                           rv_mvref_result *d_stacks, uint32_t *d_status, void *stream);
+
 /* The importance propagation of compute_block_importances
  * (src/api/internal.rs:823-1010) for one (frame, reference) pass, bit-exact
  * in f32.  org: the frame's luma plane; ref: the reference's; d_mvs,

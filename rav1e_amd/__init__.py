@@ -218,6 +218,12 @@ class RvEcModeParams(C.Structure):
                                          "last_active_segid")]
 
 
+class RvMvrefGeom(C.Structure):
+    """rv_mvref_geom (include/rav1e_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_tiles", "grid_w", "grid_h", "frame_cols",
+                                         "frame_rows")] + [("sign_bias", C.c_uint32)]
+
+
 def _declare(L):
     vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
     P = C.POINTER(RvPlane)
@@ -363,6 +369,10 @@ def _declare(L):
         "rv_ec_cand_rates": (i32, [vp, i32, vp, i32, vp, i32, RvEcModeParams, i32, vp, i32, i32,
                                    i32, i32, vp, i32, i32, vp, vp, vp, vp, C.c_uint32, vp, i32, vp,
                                    vp, vp, vp, vp]),
+        "rv_mvref_paint_scratch_bytes": (C.c_size_t, [RvMvrefGeom]),
+        "rv_mvref_grid_paint": (i32, [vp, i32, RvMvrefGeom, vp, vp, vp, vp, vp]),
+        "rv_find_mvrefs_batch": (i32, [vp, i32, RvMvrefGeom, vp, vp, vp, vp, vp]),
+        "rv_ec_mode_fill_stacks": (i32, [vp, i32, RvMvrefGeom, vp, vp, vp, vp, vp]),
         "rv_sad_fn": (vp, [i32, i32, i32]),
         "rv_satd_fn": (vp, [i32, i32, i32]),
         "rv_put_fn_get": (vp, [i32, i32, i32]),
@@ -1975,6 +1985,179 @@ def candidate_rates(committed_mode_jobs, committed_coeff_jobs, coeffs, candidate
         raise Rav1eHipError(f"candidate_rates: {rejected} candidates outside the restrictions, "
                             f"{bad} groups with a bad token or snapshot index")
     return rates, tok, off
+
+
+# ---- MV reference stacks of every block size (rv_mvstack.hip) ----------------
+# rv_mv_blk, rv_mv_cand, rv_mvref_tile, rv_mvref_query, rv_mvref_result
+MV_BLK = np.dtype([("ref", np.int8, 2), ("n4_w", np.uint8), ("n4_h", np.uint8), ("newmv", np.uint8),
+                   ("pad", np.uint8, 3), ("mv", np.int16, (2, 2))])
+MV_CAND = np.dtype([("this_mv", np.int16, 2), ("comp_mv", np.int16, 2), ("weight", np.uint32)])
+MVREF_TILE = np.dtype([(n, np.int32) for n in ("cols", "rows", "mi_x", "mi_y")])
+MVREF_QUERY = np.dtype([("tile", np.int32), ("bx", np.int32), ("by", np.int32), ("bw4", np.int32),
+                        ("bh4", np.int32), ("ref", np.int32, 2), ("reserved", np.int32)])
+MVREF_RESULT = np.dtype([("mode_context", np.int32), ("n", np.int32), ("stack", MV_CAND, 9)])
+MVREF_MAX_TILES = 1024
+
+
+def default_block_grid(n_tiles, grid_h, grid_w):
+    """Block::default() in every cell (src/context.rs:1425-1442): intra, 64x64."""
+    g = np.zeros((n_tiles, grid_h, grid_w), MV_BLK)
+    g["n4_w"] = g["n4_h"] = 16
+    return g
+
+
+def _sign_bias_mask(sign_bias):
+    if isinstance(sign_bias, (int, np.integer)):
+        m = int(sign_bias)
+    else:
+        m = sum(1 << i for i, b in enumerate(sign_bias) if b)
+    if not 0 <= m < 128:
+        raise Rav1eHipError("sign_bias: seven references' bits (RefType 1..7)")
+    return m
+
+
+class BlockGrid:
+    """Per-tile grids of MV_BLK records in device memory, with the tiles and
+    the frame they belong to (rv_mvref_geom).  tiles: rows of (cols, rows,
+    mi_x, mi_y) in 4x4 units; grid_w / grid_h default to the largest tile
+    rounded up to whole superblocks; frame_cols / frame_rows to the extent of
+    the tiles."""
+
+    def __init__(self, tiles, frame_cols=None, frame_rows=None, sign_bias=0, grid_w=None,
+                 grid_h=None):
+        t = np.asarray(tiles)
+        if t.dtype != MVREF_TILE:
+            t = np.ascontiguousarray(t, np.int32).reshape(-1, 4).view(MVREF_TILE).reshape(-1)
+        self.tiles = np.ascontiguousarray(t)
+        nt = len(self.tiles)
+        if not 1 <= nt <= MVREF_MAX_TILES:
+            raise Rav1eHipError(f"BlockGrid: {nt} tiles (1..{MVREF_MAX_TILES})")
+        if (self.tiles["cols"].min() < 1 or self.tiles["rows"].min() < 1 or
+                self.tiles["mi_x"].min() < 0 or self.tiles["mi_y"].min() < 0):
+            raise Rav1eHipError("BlockGrid: an empty tile or a negative origin")
+        up16 = lambda v: (int(v) + 15) // 16 * 16  # noqa: E731
+        self.grid_w = up16(self.tiles["cols"].max()) if grid_w is None else int(grid_w)
+        self.grid_h = up16(self.tiles["rows"].max()) if grid_h is None else int(grid_h)
+        if (self.grid_w % 16 or self.grid_h % 16 or self.grid_w < self.tiles["cols"].max() or
+                self.grid_h < self.tiles["rows"].max()):
+            raise Rav1eHipError("BlockGrid: grid_w / grid_h a multiple of 16 that holds every tile")
+        ex = int((self.tiles["mi_x"] + self.tiles["cols"]).max())
+        ey = int((self.tiles["mi_y"] + self.tiles["rows"]).max())
+        self.frame_cols = ex if frame_cols is None else int(frame_cols)
+        self.frame_rows = ey if frame_rows is None else int(frame_rows)
+        self.sign_bias = _sign_bias_mask(sign_bias)
+        self.rejected = 0
+        self.dtiles = DeviceBuffer.from_array(self.tiles)
+        self.buf = DeviceBuffer(nt * self.grid_h * self.grid_w * MV_BLK.itemsize)
+
+    @property
+    def shape(self):
+        return (len(self.tiles), self.grid_h, self.grid_w)
+
+    def geom(self):
+        return RvMvrefGeom(len(self.tiles), self.grid_w, self.grid_h, self.frame_cols,
+                           self.frame_rows, self.sign_bias)
+
+    @classmethod
+    def from_array(cls, cells, tiles, **kw):
+        """A grid the host painted: cells (n_tiles, grid_h, grid_w) MV_BLK."""
+        cells = np.ascontiguousarray(cells, MV_BLK)
+        if cells.ndim == 2:
+            cells = cells[None]
+        g = cls(tiles, grid_w=cells.shape[2], grid_h=cells.shape[1], **kw)
+        if cells.shape != g.shape:
+            raise Rav1eHipError(f"BlockGrid.from_array: cells {cells.shape}, tiles want {g.shape}")
+        g.buf.upload(cells)
+        return g
+
+    def download(self):
+        return self.buf.download(MV_BLK).reshape(self.shape)
+
+
+def paint_block_grid(jobs, tiles, frame_cols=None, frame_rows=None, sign_bias=0, grid_w=None,
+                     grid_h=None):
+    """rv_mvref_grid_paint: the blocks (kind 0) of a coding-order EC_MODE_JOB
+    list painted into per-tile grids of MV_BLK, every other cell
+    Block::default(); where jobs overlap, the later one wins.  Returns the
+    device-resident BlockGrid; .rejected counts the jobs that painted nothing
+    (outside their tile, a 128 size, bad references or MVs)."""
+    jobs = np.ascontiguousarray(jobs, EC_MODE_JOB)
+    g = BlockGrid(tiles, frame_cols, frame_rows, sign_bias, grid_w, grid_h)
+    n = len(jobs)
+    if n == 0:
+        g.buf.upload(default_block_grid(*g.shape))
+        return g
+    dj = DeviceBuffer.from_array(jobs)
+    scr = DeviceBuffer(lib().rv_mvref_paint_scratch_bytes(g.geom()))
+    dst = DeviceBuffer(4)
+    _check(lib().rv_mvref_grid_paint(dj.ptr, n, g.geom(), g.dtiles.ptr, g.buf.ptr, scr.ptr, dst.ptr,
+                                     None), "rv_mvref_grid_paint")
+    _sync(None)
+    g.rejected = int(dst.download(np.uint32)[0])
+    return g
+
+
+def mvref_queries(rows):
+    """(n, 7) integers (tile, bx, by, bw4, bh4, ref0, ref1) as MVREF_QUERY."""
+    rows = np.asarray(rows, np.int64).reshape(-1, 7)
+    q = np.zeros(len(rows), MVREF_QUERY)
+    for k, f in enumerate(("tile", "bx", "by", "bw4", "bh4")):
+        q[f] = rows[:, k]
+    q["ref"] = rows[:, 5:7]
+    return q
+
+
+def find_mvrefs_batch(grid, queries, results=None):
+    """rv_find_mvrefs_batch: find_mvrefs (src/context.rs:2943-2965) of every
+    query against a BlockGrid in one launch.  queries: MVREF_QUERY, or rows for
+    mvref_queries.  results: an MVREF_RESULT array the output starts from (a
+    rejected query leaves its slot as it was; default zeros).  Returns
+    (mode_context [n], length [n], stacks [n, 9] MV_CAND, rejected count)."""
+    q = np.asarray(queries)
+    q = np.ascontiguousarray(q) if q.dtype == MVREF_QUERY else mvref_queries(q)
+    n = len(q)
+    res = np.zeros(n, MVREF_RESULT) if results is None else np.ascontiguousarray(results,
+                                                                                 MVREF_RESULT)
+    if len(res) != n:
+        raise Rav1eHipError("find_mvrefs_batch: one result slot per query")
+    if n == 0:
+        return res["mode_context"], res["n"], res["stack"], 0
+    dq, dr, dst = DeviceBuffer.from_array(q), DeviceBuffer.from_array(res), DeviceBuffer(4)
+    _check(lib().rv_find_mvrefs_batch(dq.ptr, n, grid.geom(), grid.dtiles.ptr, grid.buf.ptr, dr.ptr,
+                                      dst.ptr, None), "rv_find_mvrefs_batch")
+    _sync(None)
+    res = dr.download(MVREF_RESULT, n)
+    return res["mode_context"], res["n"], res["stack"], int(dst.download(np.uint32)[0])
+
+
+def ec_fill_mode_stacks(jobs, grid, check=True, info=None):
+    """rv_ec_mode_fill_stacks: mode_context, num_mv_found, weight and ref_mv of
+    every inter block of an EC_MODE_JOB list from the MV stacks of a BlockGrid
+    (the jobs' own, or the committed blocks' for a candidate list).  Returns
+    (the filled jobs, stack_mvs (n, 4, 2): the first four entries' this_mv
+    (row, col), what check_mode_jobs and ec_tokenize_modes take).  check: raise
+    when an inter job was rejected (an unsupported size, a position outside
+    its tile, bad references) instead of leaving it unfilled.  info: a dict
+    that receives "rejected" and "stacks" (the full MVREF_RESULT of every
+    filled job)."""
+    jobs = np.ascontiguousarray(jobs, EC_MODE_JOB)
+    n = len(jobs)
+    full, rejected = np.zeros(n, MVREF_RESULT), 0
+    filled = jobs.copy()
+    if n:
+        dj, ds, dst = DeviceBuffer.from_array(jobs), DeviceBuffer.from_array(full), DeviceBuffer(4)
+        _check(lib().rv_ec_mode_fill_stacks(dj.ptr, n, grid.geom(), grid.dtiles.ptr, grid.buf.ptr,
+                                            ds.ptr, dst.ptr, None), "rv_ec_mode_fill_stacks")
+        _sync(None)
+        filled = dj.download(EC_MODE_JOB, n)
+        full = ds.download(MVREF_RESULT, n)
+        rejected = int(dst.download(np.uint32)[0])
+    if info is not None:
+        info["rejected"], info["stacks"] = rejected, full
+    if check and rejected:
+        raise Rav1eHipError(f"ec_fill_mode_stacks: {rejected} inter jobs outside the supported "
+                            "sizes, their tile or the reference codes")
+    return filled, full["stack"]["this_mv"][:, :4].astype(np.int32)
 
 
 def prep_8tap_batch(src: DevicePlane, jobs, w, h, mode_x=0, mode_y=0, bit_depth=8):
