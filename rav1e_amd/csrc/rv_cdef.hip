@@ -19,8 +19,6 @@
 
 namespace rv {
 
-constexpr int kCdefVeryLarge = 0x8000;
-
 struct CdefArgs {
   rv_plane src, dst;
   const uint8_t *skip, *cdef_index, *dir;
@@ -44,8 +42,6 @@ __device__ __forceinline__ int cdef_px(const rv_plane &p, int pw, int ph, int x,
     return ((const T *)p.data)[(int64_t)(p.yorigin + y) * p.stride + p.xorigin + x];
   return (x >= -2 && x < pw + 2 && y >= -2 && y < ph + 2) ? kCdefVeryLarge : 128;
 }
-
-__device__ __forceinline__ int cdef_msb(int32_t x) { return 31 ^ __clz(x); }
 
 __device__ __forceinline__ bool cdef_skip8(const uint8_t *skip, int mi_stride, int bx, int by) {
   const uint8_t *s = skip + (int64_t)(2 * by) * mi_stride + 2 * bx;
@@ -129,26 +125,6 @@ __global__ __launch_bounds__(256) void cdef_dir_kernel(CdefArgs a) {
   a.dir_out[i] = dir;
   a.var_out[i] = var;
 }
-
-// constrain (src/cdef.rs:134-148)
-__device__ __forceinline__ int cdef_constrain(int diff, int threshold, int damping) {
-  if (!threshold) return 0;
-  const int shift = max(0, damping - cdef_msb(threshold));
-  const int ad = diff < 0 ? -diff : diff;
-  const int mag = min(ad, max(0, threshold - (ad >> shift)));
-  return diff < 0 ? -mag : mag;
-}
-
-// adjust_strength (src/cdef.rs:232-239)
-__device__ __forceinline__ int cdef_adjust(int strength, int32_t var) {
-  const int i = (var >> 6) ? min(cdef_msb(var >> 6), 12) : 0;
-  return var ? (strength * (4 + i) + 8) >> 4 : 0;
-}
-
-// tap offsets (dy, dx) of cdef_directions (src/cdef.rs:164-173): [dir][k]
-__constant__ int8_t kCdefDirs[8][2][2] = {
-    {{-1, 1}, {-2, 2}}, {{0, 1}, {-1, 2}}, {{0, 1}, {0, 2}},  {{0, 1}, {1, 2}},
-    {{1, 1}, {2, 2}},   {{1, 0}, {2, 1}},  {{1, 0}, {2, 0}},  {{1, 0}, {2, -1}}};
 
 template <typename T>
 __global__ __launch_bounds__(256) void cdef_filter_kernel(CdefPlanes P) {

@@ -2,11 +2,13 @@
 // gfx950: rav1e's per-unit decision (rdo_loop_decision's restoration pass,
 // src/rdo.rs:1726-2120) and lrf_filter_frame (src/lrf.rs:1345-1444).
 //
-// Three launches per frame, after the frame's reconstruction:
-//  * lrf_rdo_kernel, one workgroup per (superblock, plane) unit -- every
-//    unit is one superblock at the replay's quantizers (RestorationState::
-//    new, base_q_idx <= 160): the unit's input as rav1e builds it while the
-//    tile is coded (the reconstruction so far, 128 where a superblock is not
+// Three steps per frame, after the frame's reconstruction:
+//  * lrf_rdo_wide_kernel (the 64 x 64 units: luma, 4:4:4 chroma) and
+//    lrf_rdo_kernel (the 32 x 32 units of 4:2:0 chroma), one workgroup per
+//    (superblock, plane) unit -- every unit is one superblock at the
+//    replay's quantizers (RestorationState::new, base_q_idx <= 160): the
+//    unit's input as rav1e builds it while the tile is coded (the
+//    reconstruction so far, 128 where a superblock is not
 //    coded yet, CDEF_VERY_LARGE outside the tile, CDEF index 0 on top), its
 //    integral images in LDS, then None and each of the 16 parameter sets:
 //    the box (a, b) tables in LDS, sgrproj_solve's sums (exact i64 block
@@ -29,13 +31,14 @@
 #include <type_traits>
 #include <string.h>
 
+#include "rv_cdef.h"
 #include "rv_device.h"
+#include "rv_distortion.h"
 #include "rv_lrf.h"
 
 namespace rv {
 namespace {
 
-constexpr int kVeryLarge = 0x8000;
 constexpr int kRstBits = 4, kPrjBits = 7, kSgrBits = 8, kMtableBits = 20, kRecipBits = 12;
 
 // SGRPROJ_PARAMS_S (src/lrf.rs:61-78)
@@ -43,27 +46,9 @@ __constant__ uint32_t kSgrS[16][2] = {{140, 3236}, {112, 2158}, {93, 1618}, {80,
                                       {70, 1295},  {58, 1177},  {47, 1079}, {37, 996},
                                       {30, 925},   {25, 863},   {0, 2589},  {0, 1618},
                                       {0, 1177},   {0, 925},    {56, 0},    {22, 0}};
-// cdef_directions (src/cdef.rs:164-173): [dir][k] = (dy, dx)
-__constant__ int8_t kLrfCdefDirs[8][2][2] = {
-    {{-1, 1}, {-2, 2}}, {{0, 1}, {-1, 2}}, {{0, 1}, {0, 2}}, {{0, 1}, {1, 2}},
-    {{1, 1}, {2, 2}},   {{1, 0}, {2, 1}},  {{1, 0}, {2, 0}}, {{1, 0}, {2, -1}}};
-
-__device__ __forceinline__ int msb32(int32_t x) { return 31 ^ __clz(x); }
-__device__ __forceinline__ int iclamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // ---- CDEF of one pixel of the unit's padded input (cdef_filter_block,
-// src/cdef.rs:134-228) --------------------------------------------------------
-__device__ __forceinline__ int cdef_constrain(int diff, int threshold, int damping) {
-  if (!threshold) return 0;
-  const int shift = max(0, damping - msb32(threshold));
-  const int ad = diff < 0 ? -diff : diff;
-  const int mag = min(ad, max(0, threshold - (ad >> shift)));
-  return diff < 0 ? -mag : mag;
-}
-__device__ __forceinline__ int cdef_adjust(int strength, int32_t var) {  // :232-239
-  const int i = (var >> 6) ? min(msb32(var >> 6), 12) : 0;
-  return var ? (strength * (4 + i) + 8) >> 4 : 0;
-}
+// src/cdef.rs:134-228; its primitives: rv_cdef.h) ------------------------------
 // the taps' offsets in a buffer of pitch s: [dir][k][primary, the two
 // secondaries], from cdef_directions (one lane per entry)
 __device__ __forceinline__ void cdef_offsets(int16_t *offs, int s) {
@@ -71,7 +56,7 @@ __device__ __forceinline__ void cdef_offsets(int16_t *offs, int s) {
   if (t < 48) {
     const int dir = t / 6, k = (t / 3) & 1, j = t % 3;
     const int d = j == 0 ? dir : j == 1 ? (dir + 2) & 7 : (dir + 6) & 7;
-    offs[t] = (int16_t)(kLrfCdefDirs[d][k][0] * s + kLrfCdefDirs[d][k][1]);
+    offs[t] = (int16_t)(kCdefDirs[d][k][0] * s + kCdefDirs[d][k][1]);
   }
 }
 // in: the padded u16 input at the pixel; off: cdef_offsets of its direction
@@ -85,44 +70,18 @@ __device__ inline int cdef_px(const uint16_t *in, const int16_t *off, int pri, i
     const int d0 = off[3 * k], d1 = off[3 * k + 1], d2 = off[3 * k + 2];
     const int p0 = in[d0], p1 = in[-d0];
     sum += pt * (cdef_constrain(p0 - x, pri, damping) + cdef_constrain(p1 - x, pri, damping));
-    if (p0 != kVeryLarge) mx = max(p0, mx);
-    if (p1 != kVeryLarge) mx = max(p1, mx);
+    if (p0 != kCdefVeryLarge) mx = max(p0, mx);
+    if (p1 != kCdefVeryLarge) mx = max(p1, mx);
     mn = min(min(p0, p1), mn);
     const int sv[4] = {in[d1], in[-d1], in[d2], in[-d2]};
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-      if (sv[e] != kVeryLarge) mx = max(sv[e], mx);
+      if (sv[e] != kCdefVeryLarge) mx = max(sv[e], mx);
       mn = min(sv[e], mn);
       sum += st * cdef_constrain(sv[e] - x, sec, damping);
     }
   }
-  return iclamp(x + ((8 + sum - (sum < 0)) >> 4), mn, mx);
-}
-// ---- distortion (src/rdo.rs) -------------------------------------------------
-// compute_distortion_bias of an 8x8 at 4x4 block (mi_x, mi_y) (src/rdo.rs:
-// 476-508): f32 mean of its importance cells / 3 + 0.65
-__device__ inline double lrf_bias(const float *imp, int w_imp, int w_in_b, int h_in_b, int mi_x,
-                                  int mi_y) {
-  if (!imp) return 0.65;
-  const int x2 = min(mi_x + 2, w_in_b), y2 = min(mi_y + 2, h_in_b);
-  float tot = 0.f;
-  for (int y = mi_y; y < y2; y++)
-    for (int x = mi_x; x < x2; x++) tot = __fadd_rn(tot, imp[(y >> 1) * w_imp + (x >> 1)]);
-  return (double)__fdiv_rn(__fdiv_rn(tot, 4.0f), 3.0f) + 0.65;
-}
-__device__ __forceinline__ uint64_t biased(uint64_t v, double b) { return (uint64_t)((double)v * b); }
-// cdef_dist_wxh_8x8's f64 tail (src/rdo.rs:219-261) from the moments
-__device__ inline uint64_t cdef_dist(int32_t ss, int32_t sd, uint32_t ss2, uint32_t sd2, uint32_t ssd,
-                                     int bd) {
-  const int cs = bd - 8;
-  const int64_t s2 = (int64_t)ss2, d2 = (int64_t)sd2, sdv = (int64_t)ssd;
-  const double svar = (double)(s2 - (((int64_t)ss * ss + 32) >> 6));
-  const double dvar = (double)(d2 - (((int64_t)sd * sd + 32) >> 6));
-  const double sse = (double)(d2 + s2 - 2 * sdv);
-  const double boost = (4033.0 / 16384.0) * (svar + dvar + (double)(16384ll << (2 * cs))) /
-                       sqrt((double)(16265089ull << (4 * cs)) + svar * dvar);
-  const double v = sse * boost + 0.5;
-  return v > 0.0 ? (uint64_t)v : 0;
+  return clampi(x + ((8 + sum - (sum < 0)) >> 4), mn, mx);
 }
 
 // ---- the self-guided filter (src/lrf.rs:156-334) ------------------------------
@@ -349,7 +308,7 @@ __device__ __forceinline__ int sgr_out(uint32_t f2, uint32_t f1, uint32_t px, in
   const int32_t u = (int32_t)(px << kRstBits);
   const int32_t v = w0 * (int32_t)f2 + w1 * u + ((1 << kPrjBits) - w0 - w1) * (int32_t)f1;
   constexpr int sh = kRstBits + kPrjBits;
-  return iclamp((v + ((1 << sh) >> 1)) >> sh, 0, mx);
+  return clampi((v + ((1 << sh) >> 1)) >> sh, 0, mx);
 }
 
 // inclusive u32 prefix sums (wrapping) of the image's lines -- rows of ii
@@ -523,16 +482,10 @@ struct LrfRdoArgs {
   int8_t *xqd;               // [3][nsb][16][2]
 };
 
-// One workgroup per unit, BW * BH / 4 lanes: a lane owns a column strip of
-// 4 pixels (x, y0 .. y0 + 3) -- one table read serves all four -- and keeps
-// its f values in registers from the solve sums to the filtered pixels.
-// 64 x 64 units (luma, 4:4:4 chroma): 1024 lanes, ~135 KB of LDS, one per
-// CU; 32 x 32 (4:2:0 chroma): 256 lanes, ~36 KB, several per CU. The
-// boxes' (p, sum) are set-independent: computed once, each set's (a, b)
-// tables are a multiply and a table lookup per entry. The distortion of an
-// option comes from the lanes' registers: 64-wide units sum half blocks
-// over 8 lanes and the last wave joins the halves; 4:2:0 chroma sums 2x2
-// parts over lane pairs.
+// One workgroup per unit, two kernels: lrf_rdo_wide_kernel prices the
+// 64 x 64 units (luma, 4:4:4 chroma), lrf_rdo_kernel the 32 x 32 units of
+// 4:2:0 chroma. Both take the steps below from one place; the lanes' strip
+// layout, the tables' build and the distortion's parts are each kernel's own.
 #ifdef LRF_PHASES  // tools/ubench/lrf_bench.hip: one workgroup's phase clocks
 __device__ unsigned long long lrf_phase_t[96];
 #define PHASE(k) \
@@ -541,10 +494,171 @@ __device__ unsigned long long lrf_phase_t[96];
 #define PHASE(k)
 #endif
 
-template <int BW, int BH>
+// What both kernels derive from (LrfRdoArgs, plane, superblock).
+struct LrfUnit {
+  int fsx, fsy;          // the superblock in the frame
+  int t0x, t0y, sx, sy;  // its tile's first superblock, the superblock in the tile
+  int xd, yd;            // the plane's decimation
+  int pw_t, ph_t;        // the tile in plane pixels
+  int mi_cols, mi_rows;  // the tile in 4x4 luma blocks
+  int ox, oy, fx0, fy0;  // the unit in the tile, the tile in the frame plane
+  int uw, uh;            // the unit (its size clipped at the tile-relative offset, the reference's quirk)
+  int vw, vh;            // its part inside the tile
+  int elx, ely;          // the part its 8x8 luma blocks inside the tile cover (the distortion's)
+  int bd, cs, mx;
+};
+// the unit of up to bw x bh pixels at superblock sb of plane p; false (for
+// the whole workgroup): no unit there, or another group's. (Arithmetic only
+// and one exit: behind an early return the compiler loses uw <= bw and
+// uh <= bh, which size the unrolled chunks of the prefix sums.)
+__device__ __forceinline__ bool lrf_unit(const LrfRdoArgs &a, int p, int sb, int bw, int bh, LrfUnit &u) {
+  const LrfGeo &g = a.g;
+  u.fsx = sb % g.sbc;
+  u.fsy = sb / g.sbc;
+  u.t0x = u.fsx - u.fsx % g.tws;
+  u.t0y = u.fsy - u.fsy % g.ths;
+  u.sx = u.fsx - u.t0x;
+  u.sy = u.fsy - u.t0y;
+  u.xd = p ? g.xdec : 0;
+  u.yd = p ? g.ydec : 0;
+  const int tw_px = min(g.tws * 64, g.W - u.t0x * 64), th_px = min(g.ths * 64, g.H - u.t0y * 64);
+  u.pw_t = (tw_px + u.xd) >> u.xd;
+  u.ph_t = (th_px + u.yd) >> u.yd;
+  u.mi_cols = tw_px >> 2;
+  u.mi_rows = th_px >> 2;
+  u.ox = (u.sx * 64) >> u.xd;
+  u.oy = (u.sy * 64) >> u.yd;
+  u.fx0 = (u.t0x * 64) >> u.xd;
+  u.fy0 = (u.t0y * 64) >> u.yd;
+  const int pw = p ? (g.W + u.xd) >> u.xd : g.W, ph = p ? (g.H + u.yd) >> u.yd : g.H;
+  u.uw = min(bw, pw - u.ox);
+  u.uh = min(bh, ph - u.oy);
+  u.vw = min(bw, u.pw_t - u.ox);
+  u.vh = min(bh, u.ph_t - u.oy);
+  u.elx = (min(8, max(0, (u.mi_cols - u.sx * 16 + 1) / 2)) * 8) >> u.xd;
+  u.ely = (min(8, max(0, (u.mi_rows - u.sy * 16 + 1) / 2)) * 8) >> u.yd;
+  u.bd = g.bd;
+  u.cs = g.bd - 8;
+  u.mx = (1 << g.bd) - 1;
+  return u.fsx < g.cols[p] && u.fsy < g.rows[p] &&  // a unit
+         u.fsx >= a.gx0 && u.fsx < a.gx1 && u.fsy >= a.gy0 && u.fsy < a.gy1;  // this group's
+}
+
+// Step 1 of a unit's input (NT lanes): the padded copy of the reconstruction
+// so far -- 128 where a superblock is not coded yet, CDEF_VERY_LARGE outside
+// the tile -- at pad (pitch BW + 4, with coffs its tap offsets), and
+// lrf_input before CDEF at lin (pitch BW). No barrier.
+template <typename Px, int BW, int BH, int NT>
+__device__ __forceinline__ void lrf_unit_copy(const rv_plane &rec, const LrfUnit &u, uint16_t *pad,
+                                              uint16_t *lin, int16_t *coffs) {
+  const int tid = threadIdx.x;
+  auto recpx = [&](int x, int y) __attribute__((always_inline)) -> int {  // frame plane coordinates
+    return (int)((const Px *)rec.data)[(int64_t)(rec.yorigin + y) * rec.stride + rec.xorigin + x];
+  };
+  cdef_offsets(coffs, BW + 4);
+  for (int i = tid; i < (BH + 4) * (BW + 4); i += NT) {
+    const int y = i / (BW + 4) - 2, x = i % (BW + 4) - 2, tx = u.ox + x, ty = u.oy + y;
+    int v = kCdefVeryLarge;
+    if (tx >= 0 && tx < u.pw_t && ty >= 0 && ty < u.ph_t) {
+      const int csx = (tx << u.xd) >> 6, csy = (ty << u.yd) >> 6;
+      v = (csy < u.sy || (csy == u.sy && csx <= u.sx)) ? recpx(u.fx0 + tx, u.fy0 + ty) : 128;
+    }
+    pad[i] = (uint16_t)v;
+  }
+  for (int i = tid; i < BW * BH; i += NT) {
+    const int y = i / BW, x = i % BW;
+    lin[i] = (uint16_t)recpx(u.fx0 + u.ox + min(x, u.vw - 1), u.fy0 + u.oy + min(y, u.vh - 1));
+  }
+}
+// Step 2: CDEF index 0 on the 8x8 blocks inside the tile
+// (cdef_filter_superblock), pad -> lin; the blocks' skip / dir / var go
+// through bskip, bdir and bvar (64 each), one barrier after them. The
+// caller's barrier follows.
+template <int BW, int BH, int NT>
+__device__ __forceinline__ void lrf_unit_cdef(const LrfRdoArgs &a, int p, const LrfUnit &u, const uint16_t *pad,
+                                              uint16_t *lin, const int16_t *coffs, uint8_t *bskip,
+                                              uint8_t *bdir, int32_t *bvar) {
+  if (!a.cdef) return;
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    const int bx = tid & 7, by = tid >> 3, gx = u.sx * 16 + 2 * bx, gy = u.sy * 16 + 2 * by;
+    uint8_t sk = 2, dir = 0;
+    int32_t var = 0;
+    if (gx < u.mi_cols && gy < u.mi_rows) {
+      const uint8_t *k = a.skip + (int64_t)(u.t0y * 16 + gy) * a.mi_stride + u.t0x * 16 + gx;
+      sk = k[0] & k[1] & k[a.mi_stride] & k[a.mi_stride + 1];
+      if (!sk) {
+        const int64_t o = (int64_t)(u.fsy * 8 + by) * a.dstride + u.fsx * 8 + bx;
+        dir = a.dir[o];
+        var = a.var[o];
+      }
+    }
+    bskip[tid] = sk;
+    bdir[tid] = dir;
+    bvar[tid] = var;
+  }
+  __syncthreads();
+  const int bxs = 8 >> u.xd, bys = 8 >> u.yd, cs = u.cs;
+  for (int i = tid; i < BW * BH; i += NT) {
+    const int y = i / BW, x = i % BW, blk = (y / bys) * 8 + x / bxs;
+    if (bskip[blk]) continue;  // skip: the copy (equal to lin); 2: outside the tile
+    int pri, sec, dmp = a.damping + cs, d;
+    if (p == 0) {
+      pri = cdef_adjust(a.pri_y << cs, bvar[blk]);
+      sec = a.sec_y << cs;
+      d = a.pri_y ? bdir[blk] : 0;
+    } else {
+      pri = a.pri_uv << cs;
+      sec = a.sec_uv << cs;
+      dmp -= 1;
+      d = a.pri_uv ? bdir[blk] : 0;
+    }
+    lin[i] = (uint16_t)cdef_px(pad + (y + 2) * (BW + 4) + x + 2, coffs + 6 * d, pri, sec, dmp, cs);
+  }
+}
+
+// The solve of one set, in its two halves around the caller's barrier: the
+// lane's five sums (H00, H11, H01, C0, C1) added up per wave into red5 ...
+template <int NW>
+__device__ __forceinline__ void lrf_solve_sums(const int64_t v[5], int64_t (*red5)[NW]) {
+#pragma unroll
+  for (int q = 0; q < 5; q++) {
+    const int64_t t = (int64_t)dpp_sum64((uint64_t)v[q]);
+    if ((threadIdx.x & 63) == 0) red5[q][threadIdx.x >> 6] = t;
+  }
+}
+// ... and wave 0's solve (lanes 0 .. 4 add up one sum each): the set's xqd to
+// sxqd (for the workgroup, after the caller's next barrier) and to xo
+template <int NW>
+__device__ __forceinline__ void lrf_solve_wave0(int set, const LrfUnit &u, const int64_t (*red5)[NW],
+                                                int8_t *sxqd, int8_t *xo) {
+  const int tid = threadIdx.x;
+  int64_t t = 0;
+  if (tid < 5)
+    for (int w = 0; w < NW; w++) t += red5[tid][w];
+  const int64_t h00 = readlane64((uint64_t)t, 0), h11 = readlane64((uint64_t)t, 1),
+                h01 = readlane64((uint64_t)t, 2), c0 = readlane64((uint64_t)t, 3),
+                c1 = readlane64((uint64_t)t, 4);
+  int8_t q[2];
+  lrf_solve_finish_wave(set, u.uw, u.uh, h00, h01, h11, c0, c1, q);
+  if (tid == 0) {
+    sxqd[0] = q[0];
+    sxqd[1] = q[1];
+    xo[2 * set] = q[0];
+    xo[2 * set + 1] = q[1];
+  }
+}
+
+// 32 x 32 units (4:2:0 chroma) in 256-lane workgroups with ~35 KB of LDS,
+// several per CU: a lane owns a column strip of 4 pixels (x, y0 .. y0 + 3)
+// -- one table read serves all four -- and keeps its f values in registers
+// from the solve sums to the filtered pixels. The boxes' (p, sum) are
+// set-independent: computed once, each set's (a, b) tables are a multiply
+// and a table lookup per entry. The distortion of an option comes from the
+// lanes' registers, summed in 2x2 parts over lane pairs.
 struct RdoLds {
+  static constexpr int BW = 32, BH = 32, NT = BW * BH / 4, NW = NT / 64;
   using L = SgrLds<BW, BH>;
-  static constexpr int NT = BW * BH / 4, NW = NT / 64;
   union {
     uint32_t img[2 * L::IR * L::IS];  // ii, sq
     uint2 tab[L::TAB];                // then each set's (a, b)
@@ -560,125 +674,52 @@ struct RdoLds {
   uint8_t bdir[64], bskip[64];
   int32_t bvar[64];
   int64_t red5[5][NW];
-  uint3 hm[(BH / 4) * 8];  // 64-wide: each half block's (sd, sd2, ssd) / (sse), [strip][block column]
-  uint64_t wsum[NW];       // 4:2:0 chroma: each wave's biased part errors
-  int32_t bss[64];         // luma: each block's source sum and sum of squares
-  uint32_t bss2[64];
+  uint64_t wsum[NW];  // each wave's biased part errors
   int8_t sxqd[2];
 };
 
-template <typename Px, int BW, int BH>
-__global__ __launch_bounds__(BW * BH / 4) void lrf_rdo_kernel(LrfRdoArgs a) {
-  using Lds = RdoLds<BW, BH>;
-  using SL = SgrLds<BW, BH>;
-  constexpr int NT = Lds::NT, NW = Lds::NW, AS = SL::AS, A1R = SL::A1R;
-  constexpr int LBW = BW == 64 ? 6 : 5;
-  constexpr bool WIDE = BW == 64;  // luma / 4:4:4 chroma; else 4:2:0 chroma
-  __shared__ Lds S;
-  const LrfGeo &g = a.g;
+template <typename Px>
+__global__ __launch_bounds__(RdoLds::NT) void lrf_rdo_kernel(LrfRdoArgs a) {
+  using SL = RdoLds::L;
+  constexpr int BW = RdoLds::BW, BH = RdoLds::BH, NT = RdoLds::NT, NW = RdoLds::NW;
+  constexpr int AS = SL::AS, A1R = SL::A1R, npx = BW * BH;
+  __shared__ RdoLds S;
   const int p = a.p0 + blockIdx.y, sb = blockIdx.x, tid = threadIdx.x;
-  const int sbc = g.sbc, fsx = sb % sbc, fsy = sb / sbc;
-  if (fsx >= g.cols[p] || fsy >= g.rows[p]) return;  // no unit (uniform)
-  if (fsx < a.gx0 || fsx >= a.gx1 || fsy < a.gy0 || fsy >= a.gy1) return;  // another group's
-  const int t0x = fsx - fsx % g.tws, t0y = fsy - fsy % g.ths, sx = fsx - t0x, sy = fsy - t0y;
-  const int xd = p ? g.xdec : 0, yd = p ? g.ydec : 0;
-  constexpr int npx = BW * BH;
-  const int tw_px = min(g.tws * 64, g.W - t0x * 64), th_px = min(g.ths * 64, g.H - t0y * 64);
-  const int pw_t = (tw_px + xd) >> xd, ph_t = (th_px + yd) >> yd;
-  const int mi_cols = tw_px >> 2, mi_rows = th_px >> 2;
-  const int ox = (sx * 64) >> xd, oy = (sy * 64) >> yd, fx0 = (t0x * 64) >> xd, fy0 = (t0y * 64) >> yd;
-  const int bd = g.bd, cs = bd - 8, mx = (1 << bd) - 1;
-  const rv_plane &rec = a.rec[p], &src = a.src[p];
-  auto recpx = [&](int x, int y) -> int {  // frame plane coordinates
-    return (int)((const Px *)rec.data)[(int64_t)(rec.yorigin + y) * rec.stride + rec.xorigin + x];
-  };
+  LrfUnit u;
+  if (!lrf_unit(a, p, sb, BW, BH, u)) return;
+  const int uw = u.uw, uh = u.uh;
+  const rv_plane &src = a.src[p];
   PHASE(0);
   sgr_init_xz(S.xz);
-  cdef_offsets(S.coffs, BW + 4);
   // 1. the padded copy and the unit's input
-  for (int i = tid; i < (BH + 4) * (BW + 4); i += NT) {
-    const int y = i / (BW + 4) - 2, x = i % (BW + 4) - 2, tx = ox + x, ty = oy + y;
-    int v = kVeryLarge;
-    if (tx >= 0 && tx < pw_t && ty >= 0 && ty < ph_t) {
-      const int csx = (tx << xd) >> 6, csy = (ty << yd) >> 6;
-      v = (csy < sy || (csy == sy && csx <= sx)) ? recpx(fx0 + tx, fy0 + ty) : 128;
-    }
-    S.pad[i] = (uint16_t)v;
-  }
-  const int vw = min(BW, pw_t - ox), vh = min(BH, ph_t - oy);
-  for (int i = tid; i < npx; i += NT) {
-    const int y = i >> LBW, x = i & (BW - 1);
-    S.b.lin[i] = (uint16_t)recpx(fx0 + ox + min(x, vw - 1), fy0 + oy + min(y, vh - 1));
-  }
-  // the unit (unit size clipped at the tile-relative offset, the
-  // reference's quirk) and the two source tiles: sgrproj_solve's, read at
-  // the unit's tile-relative offset of the whole frame (ts.input with
-  // loop_tile_po, src/rdo.rs:2028-2033), and the distortion's, over the 8x8
-  // blocks inside the tile (a block reaches at most 7 past the frame, into
-  // the plane's padding)
-  const int pw = p ? (g.W + xd) >> xd : g.W, ph = p ? (g.H + yd) >> yd : g.H;
-  const int uw = min(BW, pw - ox), uh = min(BH, ph - oy);
-  const int64_t ss_ = src.stride;
-  const Px *const sp = (const Px *)src.data;
-  const int elx = (min(8, max(0, (mi_cols - sx * 16 + 1) / 2)) * 8) >> xd;
-  const int ely = (min(8, max(0, (mi_rows - sy * 16 + 1) / 2)) * 8) >> yd;
+  lrf_unit_copy<Px, BW, BH, NT>(a.rec[p], u, S.pad, S.b.lin, S.coffs);
+  // the two source tiles: sgrproj_solve's, read at the unit's tile-relative
+  // offset of the whole frame (ts.input with loop_tile_po, src/rdo.rs:
+  // 2028-2033), and the distortion's, over the 8x8 blocks inside the tile (a
+  // block reaches at most 7 past the frame, into the plane's padding)
   {
-    const Px *const ssolve = sp + (int64_t)(src.yorigin + oy) * ss_ + src.xorigin + ox;
-    const Px *const sdist = sp + (int64_t)(src.yorigin + fy0 + oy) * ss_ + src.xorigin + fx0 + ox;
+    const int64_t ss_ = src.stride;
+    const Px *const sp = (const Px *)src.data;
+    const Px *const ssolve = sp + (int64_t)(src.yorigin + u.oy) * ss_ + src.xorigin + u.ox;
+    const Px *const sdist = sp + (int64_t)(src.yorigin + u.fy0 + u.oy) * ss_ + src.xorigin + u.fx0 + u.ox;
     for (int i = tid; i < npx; i += NT) {
-      const int y = i >> LBW, x = i & (BW - 1);
+      const int y = i / BW, x = i % BW;
       S.ssolve[i] = (x < uw && y < uh) ? (uint16_t)ssolve[(int64_t)y * ss_ + x] : 0;
-      S.esrc[i] = (x < elx && y < ely) ? (uint16_t)sdist[(int64_t)y * ss_ + x] : 0;
+      S.esrc[i] = (x < u.elx && y < u.ely) ? (uint16_t)sdist[(int64_t)y * ss_ + x] : 0;
     }
   }
-  // 2. CDEF index 0 on the 8x8 blocks inside the tile (cdef_filter_superblock)
+  // 2. CDEF index 0 on the 8x8 blocks inside the tile
   PHASE(1);
-  if (a.cdef) {
-    if (tid < 64) {
-      const int bx = tid & 7, by = tid >> 3, gx = sx * 16 + 2 * bx, gy = sy * 16 + 2 * by;
-      uint8_t sk = 2, dir = 0;
-      int32_t var = 0;
-      if (gx < mi_cols && gy < mi_rows) {
-        const uint8_t *k = a.skip + (int64_t)(t0y * 16 + gy) * a.mi_stride + t0x * 16 + gx;
-        sk = k[0] & k[1] & k[a.mi_stride] & k[a.mi_stride + 1];
-        if (!sk) {
-          const int64_t o = (int64_t)(fsy * 8 + by) * a.dstride + fsx * 8 + bx;
-          dir = a.dir[o];
-          var = a.var[o];
-        }
-      }
-      S.bskip[tid] = sk;
-      S.bdir[tid] = dir;
-      S.bvar[tid] = var;
-    }
-    __syncthreads();
-    const int bxs = 8 >> xd, bys = 8 >> yd;
-    for (int i = tid; i < npx; i += NT) {
-      const int y = i >> LBW, x = i & (BW - 1), blk = (y / bys) * 8 + x / bxs;
-      if (S.bskip[blk]) continue;  // skip: the copy (equal to lin); 2: outside the tile
-      int pri, sec, dmp = a.damping + cs, d;
-      if (p == 0) {
-        pri = cdef_adjust(a.pri_y << cs, S.bvar[blk]);
-        sec = a.sec_y << cs;
-        d = a.pri_y ? S.bdir[blk] : 0;
-      } else {
-        pri = a.pri_uv << cs;
-        sec = a.sec_uv << cs;
-        dmp -= 1;
-        d = a.pri_uv ? S.bdir[blk] : 0;
-      }
-      S.b.lin[i] = (uint16_t)cdef_px(S.pad + (y + 2) * (BW + 4) + x + 2, S.coffs + 6 * d, pri, sec, dmp, cs);
-    }
-  }
+  lrf_unit_cdef<BW, BH, NT>(a, p, u, S.pad, S.b.lin, S.coffs, S.bskip, S.bdir, S.bvar);
   __syncthreads();
   // 3. the unit's integral image: lrf_input alone, replicated
   PHASE(2);
   sgr_integral<SL::IS, SL::IR>(S.a.img, uw, uh, [&](int r, int c) -> uint32_t {
-    return S.b.lin[iclamp(r - 4, 0, uh - 1) * BW + iclamp(c - 4, 0, uw - 1)];
+    return S.b.lin[clampi(r - 4, 0, uh - 1) * BW + clampi(c - 4, 0, uw - 1)];
   });
   // the lane's column strip (qx, qy0 .. qy0 + 3): its input pixels
   PHASE(3);
-  const int qx = tid & (BW - 1), qy0 = (tid >> LBW) * 4;
+  const int qx = tid % BW, qy0 = (tid / BW) * 4;
   uint32_t pxr[4], lnr[4];  // the unit's pixels (0 outside it), lrf_input's
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -689,94 +730,42 @@ __global__ __launch_bounds__(BW * BH / 4) void lrf_rdo_kernel(LrfRdoArgs a) {
   __syncthreads();  // lin is read: the boxes take its place
   PHASE(4);
   const SgrLane ln = sgr_lane(uw, tid, NT);
-  sgr_boxes<SL::IS, SL::IR, AS, A1R>(S.a.img, S.b.ps, ln, uh, cs);
+  sgr_boxes<SL::IS, SL::IR, AS, A1R>(S.a.img, S.b.ps, ln, uh, u.cs);
   // 4. the distortion: rdo_loop_plane_error over the superblock's 8x8s in
-  // the tile (cdef_dist_wxh_8x8 for luma, sse_wxh in the importance
-  // block's parts for chroma), each weighted by its distortion bias
-  const int wave = tid >> 6;
-  const bool fin = wave == NW - 1;  // the last wave joins the parts
-  const int fb = tid & 63, fgx = sx * 16 + 2 * (fb & 7), fgy = sy * 16 + 2 * (fb >> 3);
-  const bool fblk = fin && fgx < mi_cols && fgy < mi_rows;  // lane fb of the last wave: block fb
-  const double fbias = fblk ? lrf_bias(a.imp, a.w_imp, a.w_in_b, a.h_in_b, t0x * 16 + fgx, t0y * 16 + fgy) : 0.0;
-  // 4:2:0 chroma: lane (qx, strip by) covers column qx of the 4x4 block
+  // the tile (sse_wxh in the importance block's parts), each weighted by its
+  // distortion bias: lane (qx, strip by) covers column qx of the 4x4 block
   // (qx / 4, by); the even lane of a pair adds up its two 2x2 parts
-  const int cgx = sx * 16 + 2 * (qx >> 2), cgy = sy * 16 + 2 * (qy0 >> 2);
-  const bool cblk = !WIDE && !(qx & 1) && cgx < mi_cols && cgy < mi_rows;
-  const double cbias = cblk ? lrf_bias(a.imp, a.w_imp, a.w_in_b, a.h_in_b, t0x * 16 + cgx, t0y * 16 + cgy) : 0.0;
-  if (WIDE && p == 0 && tid < 64) {  // luma blocks' source moments (every option reuses them)
-    int32_t ss = 0;
-    uint32_t ss2 = 0;
-    for (int j = 0; j < 8; j++)
-      for (int i = 0; i < 8; i++) {
-        const int32_t v = S.esrc[(8 * (tid >> 3) + j) * BW + 8 * (tid & 7) + i];
-        ss += v;
-        ss2 += (uint32_t)(v * v);
-      }
-    S.bss[tid] = ss;
-    S.bss2[tid] = ss2;
-  }
-  // an option's pixels d[4] (the lane's strip) -> its partial sums in LDS
+  const int wave = tid >> 6;
+  const bool fin = wave == NW - 1;  // the last wave joins the waves' sums
+  const int cgx = u.sx * 16 + 2 * (qx >> 2), cgy = u.sy * 16 + 2 * (qy0 >> 2);
+  const bool cblk = !(qx & 1) && cgx < u.mi_cols && cgy < u.mi_rows;
+  const double cbias =
+      cblk ? distortion_bias(a.imp, a.w_imp, a.w_in_b, a.h_in_b, u.t0x * 16 + cgx, u.t0y * 16 + cgy) : 0.0;
+  // an option's pixels d[4] (the lane's strip) -> its wave's sum in LDS
   auto err_part = [&](const int32_t d[4]) {
-    if (WIDE) {
-      if (p == 0) {
-        int32_t sd = 0;
-        uint32_t sd2 = 0, ssd = 0;
+    uint32_t top = 0, bot = 0;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int32_t sv = S.esrc[(qy0 + k) * BW + qx];
-          sd += d[k];
-          sd2 += (uint32_t)(d[k] * d[k]);
-          ssd += (uint32_t)(sv * d[k]);
-        }
-        sd = dpp_sum8(sd);
-        sd2 = dpp_sum8(sd2);
-        ssd = dpp_sum8(ssd);
-        if ((qx & 7) == 0) S.hm[(qy0 >> 2) * 8 + (qx >> 3)] = make_uint3((uint32_t)sd, sd2, ssd);
-      } else {  // 4:4:4 chroma: one 8x8 part per block
-        uint32_t v = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int c = (int)(int16_t)S.esrc[(qy0 + k) * BW + qx] - (int)(int16_t)d[k];
-          v += (uint32_t)(c * c);
-        }
-        v = dpp_sum8(v);
-        if ((qx & 7) == 0) S.hm[(qy0 >> 2) * 8 + (qx >> 3)] = make_uint3(v, 0, 0);
-      }
-    } else {
-      uint32_t top = 0, bot = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int c = (int)(int16_t)S.esrc[(qy0 + k) * BW + qx] - (int)(int16_t)d[k];
-        if (k < 2)
-          top += (uint32_t)(c * c);
-        else
-          bot += (uint32_t)(c * c);
-      }
-      top += dpp32<0xB1>(top);  // the lane pair (quad_perm [1,0,3,2])
-      bot += dpp32<0xB1>(bot);
-      uint64_t e = cblk ? biased(top, cbias) + biased(bot, cbias) : 0;
-      e = dpp_sum64(e);
-      if ((tid & 63) == 0) S.wsum[wave] = e;
+    for (int k = 0; k < 4; k++) {
+      const int c = (int)(int16_t)S.esrc[(qy0 + k) * BW + qx] - (int)(int16_t)d[k];
+      if (k < 2)
+        top += (uint32_t)(c * c);
+      else
+        bot += (uint32_t)(c * c);
     }
+    top += dpp32<0xB1>(top);  // the lane pair (quad_perm [1,0,3,2])
+    bot += dpp32<0xB1>(bot);
+    uint64_t e = cblk ? distortion_biased(top, cbias) + distortion_biased(bot, cbias) : 0;
+    e = dpp_sum64(e);
+    if ((tid & 63) == 0) S.wsum[wave] = e;
   };
-  uint64_t *eo = a.err + ((size_t)p * g.nsb + sb) * 17;
-  int8_t *xo = a.xqd + ((size_t)p * g.nsb + sb) * 32;
-  // option o's distortion from the parts: the last wave, after the next
-  // barrier (the parts are rewritten two barriers later)
+  uint64_t *eo = a.err + ((size_t)p * a.g.nsb + sb) * 17;
+  int8_t *xo = a.xqd + ((size_t)p * a.g.nsb + sb) * 32;
+  // option o's distortion from the waves' sums: the last wave, after the
+  // next barrier (the sums are rewritten two barriers later)
   auto err_finish = [&](int o) {
     uint64_t e = 0;
-    if (WIDE) {
-      if (fblk) {
-        const uint3 u0 = S.hm[(2 * (fb >> 3)) * 8 + (fb & 7)], u1 = S.hm[(2 * (fb >> 3) + 1) * 8 + (fb & 7)];
-        e = p == 0 ? biased(cdef_dist(S.bss[fb], (int32_t)(u0.x + u1.x), S.bss2[fb], u0.y + u1.y, u0.z + u1.z, bd),
-                            fbias)
-                   : biased((uint64_t)u0.x + u1.x, fbias);
-      }
-      e = dpp_sum64(e);
-    } else {
-      for (int w = 0; w < NW; w++) e += S.wsum[w];
-    }
-    if (fb == 0) eo[o] = (uint64_t)((double)e * a.ds[p]);
+    for (int w = 0; w < NW; w++) e += S.wsum[w];
+    if ((tid & 63) == 0) eo[o] = (uint64_t)((double)e * a.ds[p]);
   };
   {
     int32_t d[4];
@@ -804,9 +793,9 @@ __global__ __launch_bounds__(BW * BH / 4) void lrf_rdo_kernel(LrfRdoArgs a) {
 #pragma unroll
       for (int k = 0; k < 4; k++)
         if (qy0 + k < uh) {
-          const Acc u = (Acc)pxr[k] << kRstBits;
-          const Acc sv = ((Acc)S.ssolve[(qy0 + k) * BW + qx] << kRstBits) - u;
-          const Acc e2 = (Acc)(int32_t)f2r[k] - u, e1 = (Acc)(int32_t)f1r[k] - u;
+          const Acc px = (Acc)pxr[k] << kRstBits;
+          const Acc sv = ((Acc)S.ssolve[(qy0 + k) * BW + qx] << kRstBits) - px;
+          const Acc e2 = (Acc)(int32_t)f2r[k] - px, e1 = (Acc)(int32_t)f1r[k] - px;
           H00 += e2 * e2;
           H11 += e1 * e1;
           H01 += e1 * e2;
@@ -816,39 +805,21 @@ __global__ __launch_bounds__(BW * BH / 4) void lrf_rdo_kernel(LrfRdoArgs a) {
     }
     {
       const int64_t v[5] = {H00, H11, H01, C0, C1};
-#pragma unroll
-      for (int q = 0; q < 5; q++) {
-        const int64_t t = (int64_t)dpp_sum64((uint64_t)v[q]);
-        if ((tid & 63) == 0) S.red5[q][wave] = t;
-      }
+      lrf_solve_sums<NW>(v, S.red5);
     }
     __syncthreads();
     PHASE(7 + 5 * set);
-    if (wave == 0) {  // the solve (lanes 0 .. 4 add up one sum each)
-      int64_t t = 0;
-      if (tid < 5)
-        for (int w = 0; w < NW; w++) t += S.red5[tid][w];
-      const int64_t h00 = readlane64((uint64_t)t, 0), h11 = readlane64((uint64_t)t, 1),
-                    h01 = readlane64((uint64_t)t, 2), c0 = readlane64((uint64_t)t, 3),
-                    c1 = readlane64((uint64_t)t, 4);
-      int8_t q[2];
-      lrf_solve_finish_wave(set, uw, uh, h00, h01, h11, c0, c1, q);
-      if (tid == 0) {
-        S.sxqd[0] = q[0];
-        S.sxqd[1] = q[1];
-        xo[2 * set] = q[0];
-        xo[2 * set + 1] = q[1];
-      }
-    } else if (set < 15) {
+    if (wave == 0)
+      lrf_solve_wave0<NW>(set, u, S.red5, S.sxqd, xo);
+    else if (set < 15)
       sgr_tables_ps<AS, A1R>(S.b.ps, S.a.tab, S.xz, ln_rest, set + 1, uh);
-    }
     __syncthreads();
     PHASE(8 + 5 * set);
     const int w0 = S.sxqd[0], w1 = S.sxqd[1];
     int32_t d[4];
 #pragma unroll
     for (int k = 0; k < 4; k++)  // 128 outside the unit: lrf_output's fill (never inside the frame)
-      d[k] = (qx < uw && qy0 + k < uh) ? sgr_out(f2r[k], f1r[k], pxr[k], w0, w1, mx) : 128;
+      d[k] = (qx < uw && qy0 + k < uh) ? sgr_out(f2r[k], f1r[k], pxr[k], w0, w1, u.mx) : 128;
     err_part(d);
     PHASE(9 + 5 * set);
     PHASE(10 + 5 * set);
@@ -913,55 +884,25 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
   __shared__ RdoWideLds<PS> S;
   uint32_t *const img = S.raw + M::IMG, *const tab = S.raw + M::TAB;
   uint16_t *const lin = (uint16_t *)(S.raw + M::LIN), *const pad = (uint16_t *)(S.raw + M::PAD);
-  const LrfGeo &g = a.g;
   const int p = a.p0 + blockIdx.y, sb = blockIdx.x, tid = threadIdx.x;
-  const int sbc = g.sbc, fsx = sb % sbc, fsy = sb / sbc;
-  if (fsx >= g.cols[p] || fsy >= g.rows[p]) return;  // no unit (uniform)
-  if (fsx < a.gx0 || fsx >= a.gx1 || fsy < a.gy0 || fsy >= a.gy1) return;  // another group's
-  const int t0x = fsx - fsx % g.tws, t0y = fsy - fsy % g.ths, sx = fsx - t0x, sy = fsy - t0y;
-  const int xd = p ? g.xdec : 0, yd = p ? g.ydec : 0;
-  const int tw_px = min(g.tws * 64, g.W - t0x * 64), th_px = min(g.ths * 64, g.H - t0y * 64);
-  const int pw_t = (tw_px + xd) >> xd, ph_t = (th_px + yd) >> yd;
-  const int mi_cols = tw_px >> 2, mi_rows = th_px >> 2;
-  const int ox = (sx * 64) >> xd, oy = (sy * 64) >> yd, fx0 = (t0x * 64) >> xd, fy0 = (t0y * 64) >> yd;
-  const int bd = g.bd, cs = bd - 8, mx = (1 << bd) - 1;
-  const rv_plane &rec = a.rec[p], &src = a.src[p];
-  auto recpx = [&](int x, int y) __attribute__((always_inline)) -> int {  // frame plane coordinates
-    return (int)((const Px *)rec.data)[(int64_t)(rec.yorigin + y) * rec.stride + rec.xorigin + x];
-  };
+  LrfUnit u;
+  if (!lrf_unit(a, p, sb, BW, BH, u)) return;
+  const int uw = u.uw, uh = u.uh;
+  const rv_plane &src = a.src[p];
   PHASE(0);
   sgr_init_xz(S.xz);
-  cdef_offsets(S.coffs, BW + 4);
   // 1. the padded copy and the unit's input
-  for (int i = tid; i < (BH + 4) * (BW + 4); i += NT) {
-    const int y = i / (BW + 4) - 2, x = i % (BW + 4) - 2, tx = ox + x, ty = oy + y;
-    int v = kVeryLarge;
-    if (tx >= 0 && tx < pw_t && ty >= 0 && ty < ph_t) {
-      const int csx = (tx << xd) >> 6, csy = (ty << yd) >> 6;
-      v = (csy < sy || (csy == sy && csx <= sx)) ? recpx(fx0 + tx, fy0 + ty) : 128;
-    }
-    pad[i] = (uint16_t)v;
-  }
-  const int vw = min(BW, pw_t - ox), vh = min(BH, ph_t - oy);
-  for (int i = tid; i < BW * BH; i += NT) {
-    const int y = i >> 6, x = i & 63;
-    lin[i] = (uint16_t)recpx(fx0 + ox + min(x, vw - 1), fy0 + oy + min(y, vh - 1));
-  }
-  // the unit (size clipped at the tile-relative offset, the reference's
-  // quirk) and the lane's source pixels: sgrproj_solve's at the unit's
-  // tile-relative offset of the whole frame (src/rdo.rs:2028-2033), the
-  // distortion's over the 8x8 blocks inside the tile (two u16 per word)
-  const int pw = p ? (g.W + xd) >> xd : g.W, ph = p ? (g.H + yd) >> yd : g.H;
-  const int uw = min(BW, pw - ox), uh = min(BH, ph - oy);
-  const int elx = (min(8, max(0, (mi_cols - sx * 16 + 1) / 2)) * 8) >> xd;
-  const int ely = (min(8, max(0, (mi_rows - sy * 16 + 1) / 2)) * 8) >> yd;
+  lrf_unit_copy<Px, BW, BH, NT>(a.rec[p], u, pad, lin, S.coffs);
+  // the lane's source pixels: sgrproj_solve's at the unit's tile-relative
+  // offset of the whole frame (src/rdo.rs:2028-2033), the distortion's over
+  // the 8x8 blocks inside the tile (two u16 per word)
   const int qx = tid & 63, qy0 = (tid >> 6) * 4;  // strips (qx, qy0 + 32 j + k)
   uint32_t ssw[4], esw[4];
   {
     const int64_t ss_ = src.stride;
     const Px *const sp = (const Px *)src.data;
-    const Px *const ssolve = sp + (int64_t)(src.yorigin + oy) * ss_ + src.xorigin + ox;
-    const Px *const sdist = sp + (int64_t)(src.yorigin + fy0 + oy) * ss_ + src.xorigin + fx0 + ox;
+    const Px *const ssolve = sp + (int64_t)(src.yorigin + u.oy) * ss_ + src.xorigin + u.ox;
+    const Px *const sdist = sp + (int64_t)(src.yorigin + u.fy0 + u.oy) * ss_ + src.xorigin + u.fx0 + u.ox;
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
       uint32_t sv[2], ev[2];
@@ -969,7 +910,7 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
       for (int h = 0; h < 2; h++) {
         const int y = qy0 + 32 * ((j + h) >> 2) + ((j + h) & 3);
         sv[h] = (qx < uw && y < uh) ? (uint32_t)ssolve[(int64_t)y * ss_ + qx] : 0;
-        ev[h] = (qx < elx && y < ely) ? (uint32_t)sdist[(int64_t)y * ss_ + qx] : 0;
+        ev[h] = (qx < u.elx && y < u.ely) ? (uint32_t)sdist[(int64_t)y * ss_ + qx] : 0;
       }
       ssw[j >> 1] = sv[0] | sv[1] << 16;
       esw[j >> 1] = ev[0] | ev[1] << 16;
@@ -978,50 +919,14 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
   auto srcv = [&](const uint32_t *w, int i) __attribute__((always_inline)) -> int32_t {  // pixel i (0 .. 7) of the lane's strips
     return (int32_t)((w[i >> 1] >> (16 * (i & 1))) & 0xffff);
   };
-  // 2. CDEF index 0 on the 8x8 blocks inside the tile (cdef_filter_superblock)
+  // 2. CDEF index 0 on the 8x8 blocks inside the tile
   PHASE(1);
-  if (a.cdef) {
-    if (tid < 64) {
-      const int bx = tid & 7, by = tid >> 3, gx = sx * 16 + 2 * bx, gy = sy * 16 + 2 * by;
-      uint8_t sk = 2, dir = 0;
-      int32_t var = 0;
-      if (gx < mi_cols && gy < mi_rows) {
-        const uint8_t *k = a.skip + (int64_t)(t0y * 16 + gy) * a.mi_stride + t0x * 16 + gx;
-        sk = k[0] & k[1] & k[a.mi_stride] & k[a.mi_stride + 1];
-        if (!sk) {
-          const int64_t o = (int64_t)(fsy * 8 + by) * a.dstride + fsx * 8 + bx;
-          dir = a.dir[o];
-          var = a.var[o];
-        }
-      }
-      S.bskip[tid] = sk;
-      S.bdir[tid] = dir;
-      S.bvar[tid] = var;
-    }
-    __syncthreads();
-    const int bxs = 8 >> xd, bys = 8 >> yd;
-    for (int i = tid; i < BW * BH; i += NT) {
-      const int y = i >> 6, x = i & 63, blk = (y / bys) * 8 + x / bxs;
-      if (S.bskip[blk]) continue;  // skip: the copy (equal to lin); 2: outside the tile
-      int pri, sec, dmp = a.damping + cs, d;
-      if (p == 0) {
-        pri = cdef_adjust(a.pri_y << cs, S.bvar[blk]);
-        sec = a.sec_y << cs;
-        d = a.pri_y ? S.bdir[blk] : 0;
-      } else {
-        pri = a.pri_uv << cs;
-        sec = a.sec_uv << cs;
-        dmp -= 1;
-        d = a.pri_uv ? S.bdir[blk] : 0;
-      }
-      lin[i] = (uint16_t)cdef_px(pad + (y + 2) * (BW + 4) + x + 2, S.coffs + 6 * d, pri, sec, dmp, cs);
-    }
-  }
+  lrf_unit_cdef<BW, BH, NT>(a, p, u, pad, lin, S.coffs, S.bskip, S.bdir, S.bvar);
   __syncthreads();
   // 3. the unit's integral image: lrf_input alone, replicated
   PHASE(2);
   sgr_integral<SL::IS, SL::IR>(img, uw, uh, [&](int r, int c) -> uint32_t {
-    return lin[iclamp(r - 4, 0, uh - 1) * BW + iclamp(c - 4, 0, uw - 1)];
+    return lin[clampi(r - 4, 0, uh - 1) * BW + clampi(c - 4, 0, uw - 1)];
   });
   PHASE(3);
   uint32_t pxr[8], lnr[8];  // the unit's pixels (0 outside it), lrf_input's
@@ -1031,13 +936,16 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
     lnr[i] = lin[y * BW + qx];
     pxr[i] = (qx < uw && y < uh) ? lnr[i] : 0;
   }
-  // 4. the distortion (as lrf_rdo_kernel): half blocks over 8 lanes, the
-  // last wave joins them
+  // 4. the distortion: rdo_loop_plane_error over the superblock's 8x8s in
+  // the tile (cdef_dist_wxh_8x8 for luma, sse_wxh for 4:4:4 chroma), each
+  // weighted by its distortion bias: half blocks summed over 8 lanes, the
+  // last wave joins them (its lane fb: block fb)
   const int wave = tid >> 6;
   const bool fin = wave == NW - 1;
-  const int fb = tid & 63, fgx = sx * 16 + 2 * (fb & 7), fgy = sy * 16 + 2 * (fb >> 3);
-  const bool fblk = fin && fgx < mi_cols && fgy < mi_rows;
-  const double fbias = fblk ? lrf_bias(a.imp, a.w_imp, a.w_in_b, a.h_in_b, t0x * 16 + fgx, t0y * 16 + fgy) : 0.0;
+  const int fb = tid & 63, fgx = u.sx * 16 + 2 * (fb & 7), fgy = u.sy * 16 + 2 * (fb >> 3);
+  const bool fblk = fin && fgx < u.mi_cols && fgy < u.mi_rows;
+  const double fbias =
+      fblk ? distortion_bias(a.imp, a.w_imp, a.w_in_b, a.h_in_b, u.t0x * 16 + fgx, u.t0y * 16 + fgy) : 0.0;
   if (p == 0) {  // the luma half blocks' source moments (every option reuses them)
 #pragma unroll
     for (int j = 0; j < 2; j++) {
@@ -1054,6 +962,7 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
       if ((qx & 7) == 0) S.bsh[((qy0 >> 2) + 8 * j) * 8 + (qx >> 3)] = make_int2(ss, (int32_t)ss2);
     }
   }
+  // an option's pixels d[8] (the lane's strips) -> its half blocks' sums in LDS
   auto err_part = [&](const int32_t d[8]) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < 2; j++) {
@@ -1084,8 +993,10 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
       }
     }
   };
-  uint64_t *eo = a.err + ((size_t)p * g.nsb + sb) * 17;
-  int8_t *xo = a.xqd + ((size_t)p * g.nsb + sb) * 32;
+  uint64_t *eo = a.err + ((size_t)p * a.g.nsb + sb) * 17;
+  int8_t *xo = a.xqd + ((size_t)p * a.g.nsb + sb) * 32;
+  // option o's distortion from the half blocks: the last wave, after the
+  // next barrier (the sums are rewritten two barriers later)
   auto err_finish = [&](int o) __attribute__((always_inline)) {
     uint64_t e = 0;
     if (fblk) {
@@ -1093,11 +1004,11 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
       const uint3 u0 = S.hm[h0], u1 = S.hm[h1];
       if (p == 0) {
         const int2 s0 = S.bsh[h0], s1 = S.bsh[h1];
-        e = biased(cdef_dist(s0.x + s1.x, (int32_t)(u0.x + u1.x), (uint32_t)s0.y + (uint32_t)s1.y, u0.y + u1.y,
-                             u0.z + u1.z, bd),
-                   fbias);
+        e = distortion_biased(cdef_dist_finish(s0.x + s1.x, (int32_t)(u0.x + u1.x), (uint32_t)s0.y + (uint32_t)s1.y,
+                                               u0.y + u1.y, u0.z + u1.z, u.bd),
+                              fbias);
       } else {
-        e = biased((uint64_t)u0.x + u1.x, fbias);
+        e = distortion_biased((uint64_t)u0.x + u1.x, fbias);
       }
     }
     e = dpp_sum64(e);
@@ -1126,7 +1037,7 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
         int to, o, dd;
         sgr_row<SL::IS, AS, A1R>(r, r1rows, ln.tx, to, o, dd);
         const uint2 v = sgr_box(isq(img, SL::IS, SL::IR * SL::IS + o, dd), isq(img, SL::IS, o, dd),
-                                r < r1rows ? 9 : 25, cs);
+                                r < r1rows ? 9 : 25, u.cs);
         bp[k] = v.x;
         bs[k] = v.y;
       }
@@ -1148,7 +1059,7 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
   if (PS)
     sgr_tables_pp<AS, A1R>(pp, p16, tab, S.xz, ln, 0, uh);
   else
-    sgr_tables<SL::IS, SL::IR, AS, A1R>(img, tab, S.xz, ln, 0, uh, cs);
+    sgr_tables<SL::IS, SL::IR, AS, A1R>(img, tab, S.xz, ln, 0, uh, u.cs);
   PHASE(5);
   for (int set = 0; set < 16; set++) {
     __syncthreads();
@@ -1163,9 +1074,9 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
       for (int k = 0; k < 4; k++)
         if (qx < uw && qy0 + 32 * j + k < uh) {
           const int i = 4 * j + k;
-          const Acc u = (Acc)pxr[i] << kRstBits;
-          const Acc sv = ((Acc)srcv(ssw, i) << kRstBits) - u;
-          const Acc e2 = (Acc)(int32_t)f2r[i] - u, e1 = (Acc)(int32_t)f1r[i] - u;
+          const Acc px = (Acc)pxr[i] << kRstBits;
+          const Acc sv = ((Acc)srcv(ssw, i) << kRstBits) - px;
+          const Acc e2 = (Acc)(int32_t)f2r[i] - px, e1 = (Acc)(int32_t)f1r[i] - px;
           H00 += e2 * e2;
           H11 += e1 * e1;
           H01 += e1 * e2;
@@ -1175,34 +1086,17 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
     }
     {
       const int64_t v[5] = {H00, H11, H01, C0, C1};
-#pragma unroll
-      for (int q = 0; q < 5; q++) {
-        const int64_t t = (int64_t)dpp_sum64((uint64_t)v[q]);
-        if ((tid & 63) == 0) S.red5[q][wave] = t;
-      }
+      lrf_solve_sums<NW>(v, S.red5);
     }
     __syncthreads();
     PHASE(7 + 5 * set);
     if (wave == 0) {
-      int64_t t = 0;
-      if (tid < 5)
-        for (int w = 0; w < NW; w++) t += S.red5[tid][w];
-      const int64_t h00 = readlane64((uint64_t)t, 0), h11 = readlane64((uint64_t)t, 1),
-                    h01 = readlane64((uint64_t)t, 2), c0 = readlane64((uint64_t)t, 3),
-                    c1 = readlane64((uint64_t)t, 4);
-      int8_t q[2];
-      lrf_solve_finish_wave(set, uw, uh, h00, h01, h11, c0, c1, q);
-      if (tid == 0) {
-        S.sxqd[0] = q[0];
-        S.sxqd[1] = q[1];
-        xo[2 * set] = q[0];
-        xo[2 * set + 1] = q[1];
-      }
+      lrf_solve_wave0<NW>(set, u, S.red5, S.sxqd, xo);
     } else if (set < 15) {
       if (PS)
         sgr_tables_pp<AS, A1R>(pp, p16, tab, S.xz, ln_rest, set + 1, uh);
       else
-        sgr_tables<SL::IS, SL::IR, AS, A1R>(img, tab, S.xz, ln_rest, set + 1, uh, cs);
+        sgr_tables<SL::IS, SL::IR, AS, A1R>(img, tab, S.xz, ln_rest, set + 1, uh, u.cs);
     }
     __syncthreads();
     PHASE(8 + 5 * set);
@@ -1210,7 +1104,7 @@ __global__ __launch_bounds__(512, 4) void lrf_rdo_wide_kernel(LrfRdoArgs a) {
     int32_t d[8];
 #pragma unroll
     for (int i = 0; i < 8; i++)  // 128 outside the unit: lrf_output's fill (never inside the frame)
-      d[i] = (qx < uw && qy0 + 32 * (i >> 2) + (i & 3) < uh) ? sgr_out(f2r[i], f1r[i], pxr[i], w0, w1, mx) : 128;
+      d[i] = (qx < uw && qy0 + 32 * (i >> 2) + (i & 3) < uh) ? sgr_out(f2r[i], f1r[i], pxr[i], w0, w1, u.mx) : 128;
     err_part(d);
     PHASE(9 + 5 * set);
     PHASE(10 + 5 * set);
@@ -1734,8 +1628,8 @@ __device__ __forceinline__ void lrf_filter_chunk(SgrLds<32, 64> &L, uint16_t *bl
   const int sh = sz + (sz & 1), crop = crop_h;
   sgr_init_xz(L.xz);
   sgr_integral<L32::IS, L32::IR>(L.ii, w, sz, [&](int r, int c) -> uint32_t {
-    const int cy = iclamp(y0 - 4 + r, 0, crop - 1), ly = iclamp(cy, y0 - 2, y0 + sh + 1);
-    const int xx = iclamp(x - 4 + c, 0, crop_w - 1);
+    const int cy = clampi(y0 - 4 + r, 0, crop - 1), ly = clampi(cy, y0 - 2, y0 + sh + 1);
+    const int xx = clampi(x - 4 + c, 0, crop_w - 1);
     return (uint32_t)((ly >= y0 && ly < y0 + sh) ? at(cd, xx, ly) : at(db, xx, ly));
   });
   for (int i = threadIdx.x; i < w * sz; i += blockDim.x) {
@@ -1905,8 +1799,6 @@ int lrf_rdo_launch(const rv_plane rec[3], const rv_plane src[3], const uint8_t *
   const bool c420 = g.xdec && g.ydec;
   a.p0 = 0;
   const dim3 grid64((unsigned)g.nsb, c420 ? 1 : 3), grid32((unsigned)g.nsb, 2);
-  // (tools/ubench/lrf_bench.hip still times lrf_rdo_kernel<Px, 64, 64>, the
-  // 1024-lane, 135 KB workgroup the wide kernel replaced)
   if (rec[0].hbd)
     lrf_rdo_wide_kernel<uint16_t><<<grid64, 512, 0, s>>>(a);
   else
@@ -1915,9 +1807,9 @@ int lrf_rdo_launch(const rv_plane rec[3], const rv_plane src[3], const uint8_t *
   if (c420) {
     a.p0 = 1;
     if (rec[0].hbd)
-      lrf_rdo_kernel<uint16_t, 32, 32><<<grid32, 256, 0, s>>>(a);
+      lrf_rdo_kernel<uint16_t><<<grid32, 256, 0, s>>>(a);
     else
-      lrf_rdo_kernel<uint8_t, 32, 32><<<grid32, 256, 0, s>>>(a);
+      lrf_rdo_kernel<uint8_t><<<grid32, 256, 0, s>>>(a);
     RV_HIP_CHECK_LAUNCH();
   }
   return RV_OK;

@@ -39,6 +39,7 @@
 
 #include <type_traits>
 
+#include "rv_distortion.h"
 #include "rv_intra.h"
 #include "rv_rdo.h"
 #include "rv_tx.h"
@@ -349,32 +350,15 @@ __device__ __forceinline__ void mc_compound(const RdoArgs &a, const RdoPlane &pl
   wave_sync();  // window reads done, prediction visible
 }
 
-// compute_distortion_bias (src/rdo.rs:476-508) of the importance area of
-// m x m 4x4 blocks (BLOCK_8X8: m = 2; a chroma plane narrower than 8
-// pixels biases BLOCK_4X4 areas, m = 1) at 4x4-block (mi_x, mi_y) of the
-// frame: compute_mean_importance sums the f32 importances of the in-frame
-// 4x4 blocks in y-then-x order and divides by the full area; the bias is
-// (mean / 3) as f64 + 0.65.
+// compute_distortion_bias of the m x m 4x4 blocks at (mi_x, mi_y) of the frame
 __device__ __forceinline__ double rdo_bias(const RdoArgs &a, int mi_x, int mi_y, int m = 2) {
-  if (!a.imp) return 0.65;  // (0f32 / 3) as f64 + 0.65
-  const int x2 = mi_x + m < a.w_in_b ? mi_x + m : a.w_in_b;
-  const int y2 = mi_y + m < a.h_in_b ? mi_y + m : a.h_in_b;
-  float tot = 0.f;
-  for (int y = mi_y; y < y2; y++)
-    for (int x = mi_x; x < x2; x++) tot = __fadd_rn(tot, a.imp[(y >> 1) * a.w_imp + (x >> 1)]);
-  return (double)__fdiv_rn(__fdiv_rn(tot, (float)(m * m)), 3.0f) + 0.65;
-}
-// RawDistortion * bias (src/rdo.rs:539-544): `(value as f64 * bias) as u64`
-__device__ __forceinline__ uint64_t rdo_biased(uint64_t v, double bias) {
-  return (uint64_t)((double)v * bias);
+  return distortion_bias(a.imp, a.w_imp, a.w_in_b, a.h_in_b, mi_x, mi_y, m);
 }
 
 // cdef_dist_wxh_8x8 (src/rdo.rs:219-261) of the 8x8 block at o (plane) vs
 // d (LDS, row pitch dp): i32 / i64 moments (64 products of 12-bit pixels
 // stay below 2^30: u32 sums, one v_mad_u32_u24 per product), then the f64
 // ssim boost; `(sse * ssim_boost + 0.5) as u64`.
-__device__ __forceinline__ uint64_t rdo_cdef_finish(int32_t ss, int32_t sd, uint32_t ss2,
-                                                    uint32_t sd2, uint32_t ssd, int bd);
 template <typename Px>
 __device__ __forceinline__ uint64_t rdo_cdef_8x8(const Px *o, int64_t os, const Px *d, int dp,
                                                  int bd) {
@@ -392,19 +376,7 @@ __device__ __forceinline__ uint64_t rdo_cdef_8x8(const Px *o, int64_t os, const 
       sd2 += (uint32_t)wmul24(e, e);
       ssd += (uint32_t)wmul24(s, e);
     }
-  return rdo_cdef_finish(ss, sd, ss2, sd2, ssd, bd);
-}
-__device__ __forceinline__ uint64_t rdo_cdef_finish(int32_t ss, int32_t sd, uint32_t ss2,
-                                                    uint32_t sd2, uint32_t ssd, int bd) {
-  const int cs = bd - 8;
-  const int64_t s2 = (int64_t)ss2, d2 = (int64_t)sd2, sdv = (int64_t)ssd;
-  const double svar = (double)(s2 - (((int64_t)ss * ss + 32) >> 6));
-  const double dvar = (double)(d2 - (((int64_t)sd * sd + 32) >> 6));
-  const double sse = (double)(d2 + s2 - 2 * sdv);
-  const double boost = (4033.0 / 16384.0) * (svar + dvar + (double)(16384ll << (2 * cs))) /
-                       sqrt((double)(16265089ull << (4 * cs)) + svar * dvar);
-  const double v = sse * boost + 0.5;
-  return v > 0.0 ? (uint64_t)v : 0;
+  return cdef_dist_finish(ss, sd, ss2, sd2, ssd, bd);
 }
 
 // sse_wxh (src/rdo.rs:286-335) over the transform block's sub-blocks (bw x
@@ -429,7 +401,8 @@ __device__ __forceinline__ uint64_t rdo_sse_biased(const RdoArgs &a, const RdoJo
       value += row;
     }
     const int px = j.bx + j.ox + bx * bw, py = j.by + j.oy + by * bh;
-    acc += rdo_biased(value, rdo_bias(a, (px << a.xdec) >> 2, (py << a.ydec) >> 2, (N < 8 ? N : 8) / 4));
+    acc += distortion_biased(
+        value, rdo_bias(a, (px << a.xdec) >> 2, (py << a.ydec) >> 2, (N < 8 ? N : 8) / 4));
   }
   return acc;
 }
@@ -472,9 +445,9 @@ __device__ __forceinline__ uint64_t rdo_dist_biased(const RdoArgs &a, const RdoJ
         ssd += __shfl_xor(ssd, m, 64);
       }
       if (row == 0) {
-        const uint64_t v = rdo_cdef_finish(ss, sd, ss2, sd2, ssd, a.bd);
+        const uint64_t v = cdef_dist_finish(ss, sd, ss2, sd2, ssd, a.bd);
         const int px = j.bx + j.ox + bx * 8, py = j.by + j.oy + by * 8;
-        acc += rdo_biased(v, rdo_bias(a, px >> 2, py >> 2));
+        acc += distortion_biased(v, rdo_bias(a, px >> 2, py >> 2));
       }
     }
     return acc;
@@ -812,7 +785,7 @@ __device__ __forceinline__ uint64_t luma_dist(const RdoArgs &a, const RdoJob &j,
   const uint64_t v =
       rdo_cdef_8x8<Px>(o + (int64_t)(by * 8) * os + bx * 8, os, pred + by * 8 * 64 + bx * 8, 64, a.bd);
   const int px = j.bx + bx * 8, py = j.by + by * 8;
-  return group_sum<64>(rdo_biased(v, rdo_bias(a, px >> 2, py >> 2)));
+  return group_sum<64>(distortion_biased(v, rdo_bias(a, px >> 2, py >> 2)));
 }
 
 template <typename Px, int NPART, int MODE>

@@ -539,8 +539,11 @@ def _gpu_vs_cpu(w, h, xdec, ydec, bd, refs, frames, tiling=None, flags=0, imp=No
     (192, 128, 1, 1, 12, 1, None, _LRF),
     (256, 200, 1, 1, 8, 2, None, _LRF | RP.RV_REPLAY_SPEED6),
     # 12 bits, compound: the rounds' full-grid F4, single then compound candidates
-    # (last in the list: the ids of the cases above carry their position)
+    # (appended to the list: the ids of the cases above carry their position)
     (192, 128, 1, 1, 12, 2, None, RP.RV_REPLAY_DEBLOCK | RP.RV_REPLAY_CDEF),
+    # 8-bit 4:4:4 chroma units through lrf_rdo_wide_kernel (the packed tables
+    # with the plain sse), partial units at the right and bottom edges
+    (192, 136, 0, 0, 8, 2, None, _LRF),
 ])
 def test_gpu_replay_matches_cpu_replay(w, h, xdec, ydec, bd, refs, tiling, flags):
     _gpu_vs_cpu(w, h, xdec, ydec, bd, refs, 10, tiling, flags)
@@ -599,7 +602,7 @@ def test_gpu_lrf_decision_paths(monkeypatch, fix, passes):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("flags", [0, RP.RV_REPLAY_SPEED6])
+@pytest.mark.parametrize("flags", [0, RP.RV_REPLAY_SPEED6, _LRF])
 def test_gpu_replay_importance_bias_and_quantizer(flags):
     w, h = 256, 192
     rng = np.random.default_rng(3)

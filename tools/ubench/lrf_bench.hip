@@ -1,8 +1,12 @@
 // lrf_bench.hip -- loop restoration's decision kernels alone on a 2160p
 // 4:2:0 8-bit frame of synthetic content: the per-unit distortion kernel's
 // duration (full grid, HIP events) and one workgroup's phase clocks.
-// Build (tools/ubench/Makefile):  hipcc -DLRF_PHASES=... includes the
-// kernel source so the harness launches it directly.
+// It includes the kernel source so that it launches the kernels directly;
+// -DLRF_PHASES=N adds the phase clocks of unit N. Build, from the
+// repository's root, against the built library:
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -ffp-contract=off -DLRF_PHASES=0 \
+//     tools/ubench/lrf_bench.hip -Lrav1e_amd/lib -lrav1e_hip -Wl,-rpath,$PWD/rav1e_amd/lib \
+//     -o tools/ubench/lrf_bench
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -115,13 +119,10 @@ int main(int argc, char **argv) {
   for (int r = 0; r < reps; r++) {
     CK(hipEventRecord(e0, 0));
     a.p0 = 0;
-    if (r & 1)  // odd reps: the 1024-lane luma kernel (RAV1E_LRF_WIDE=0)
-      lrf_rdo_kernel<uint8_t, 64, 64><<<dim3(g.nsb, 1), 1024>>>(a);
-    else
-      lrf_rdo_wide_kernel<uint8_t><<<dim3(g.nsb, 1), 512>>>(a);
+    lrf_rdo_wide_kernel<uint8_t><<<dim3(g.nsb, 1), 512>>>(a);
     CK(hipEventRecord(em, 0));
     a.p0 = 1;
-    lrf_rdo_kernel<uint8_t, 32, 32><<<dim3(g.nsb, 2), 256>>>(a);
+    lrf_rdo_kernel<uint8_t><<<dim3(g.nsb, 2), 256>>>(a);
     CK(hipEventRecord(e1, 0));
     if (r & 1)
       lrf_decide_kernel<<<nt, 64>>>(d);
@@ -134,8 +135,8 @@ int main(int argc, char **argv) {
     CK(hipEventElapsedTime(&t2, e1, e2));
     float tl;
     CK(hipEventElapsedTime(&tl, e0, em));
-    printf("rep %d (%s luma, %s decision): rdo %.3f ms (luma %.3f; %d x 3 workgroups), decide %.3f ms (%d tiles)\n",
-           r, r & 1 ? "1024-lane" : "512-lane", r & 1 ? "serial" : "fixed-point", t1, tl, g.nsb, t2, nt);
+    printf("rep %d (%s decision): rdo %.3f ms (luma %.3f; %d x 3 workgroups), decide %.3f ms (%d tiles)\n", r,
+           r & 1 ? "serial" : "fixed-point", t1, tl, g.nsb, t2, nt);
     {  // the distortions and solutions, hashed (compare builds)
       std::vector<uint64_t> he((size_t)3 * g.nsb * 17);
       std::vector<int8_t> hx((size_t)3 * g.nsb * 32);
@@ -180,10 +181,7 @@ int main(int argc, char **argv) {
   }
   // one workgroup alone: its phases in wall_clock64 ticks (100 MHz)
   a.p0 = 0;
-  if (getenv("LRF_BENCH_OLD"))
-    lrf_rdo_kernel<uint8_t, 64, 64><<<dim3(LRF_PHASES + 1, 1), 1024>>>(a);
-  else
-    lrf_rdo_wide_kernel<uint8_t><<<dim3(LRF_PHASES + 1, 1), 512>>>(a);
+  lrf_rdo_wide_kernel<uint8_t><<<dim3(LRF_PHASES + 1, 1), 512>>>(a);
   CK(hipDeviceSynchronize());
   unsigned long long t[96];
   CK(hipMemcpyFromSymbol(t, HIP_SYMBOL(lrf_phase_t), sizeof(t)));
