@@ -97,7 +97,8 @@ def test_satd_max_residual_10bit():
 
 
 # ---- SSE / cdef moments ---------------------------------------------------
-@pytest.mark.parametrize("bd,xdec,ydec", [(8, 0, 0), (8, 1, 1), (10, 0, 0), (10, 1, 0)])
+@pytest.mark.parametrize("bd,xdec,ydec", [(8, 0, 0), (8, 1, 1), (10, 0, 0), (10, 1, 0),
+                                           (12, 0, 0), (12, 1, 1)])
 def test_sse_vs_oracle(bd, xdec, ydec):
     rng = np.random.default_rng(7 + bd + xdec)
     a = rand_plane(rng, 160, 160, bd)
@@ -117,7 +118,7 @@ def test_sse_vs_oracle(bd, xdec, ydec):
             np.testing.assert_array_equal(got[k], want, err_msg=str((w, h, k)))
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_cdef_moments_vs_oracle(bd):
     rng = np.random.default_rng(11 + bd)
     a = rand_plane(rng, 130, 140, bd)
@@ -169,7 +170,7 @@ def test_put_prep_vs_oracle(bd):
                 np.testing.assert_array_equal(prep[k], wantp)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_mc_avg_vs_oracle(bd):
     rng = np.random.default_rng(300 + bd)
     src = rand_plane(rng, 120, 120, bd)
@@ -186,7 +187,7 @@ def test_mc_avg_vs_oracle(bd):
             np.testing.assert_array_equal(got[h * k:h * k + h], want)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_mc_dist_fused_vs_oracle(bd):
     rng = np.random.default_rng(400 + bd)
     ref = rand_plane(rng, 200, 200, bd)
@@ -261,7 +262,7 @@ def _inv_supported(s, t):
                             np.zeros((h, w), np.uint8), s, t, 8) is not None
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_inv_random_vs_oracle(bd):
     rng = np.random.default_rng(600 + bd)
     dt = np.uint8 if bd == 8 else np.uint16
@@ -284,19 +285,21 @@ def test_inv_random_vs_oracle(bd):
                 np.testing.assert_array_equal(got[h * k:h * k + h], want, err_msg=str((s, t, k)))
 
 
-def test_diff_fwd_fused_vs_oracle():
-    rng = np.random.default_rng(700)
-    src = rand_plane(rng, 140, 140, 8)
-    pred = rand_plane(rng, 140, 140, 8)
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_diff_fwd_fused_vs_oracle(bd):
+    rng = np.random.default_rng(700 + bd - 8)
+    src = rand_plane(rng, 140, 140, bd)
+    pred = rand_plane(rng, 140, 140, bd)
     ps, pp = R.DevicePlane.from_array(src), R.DevicePlane.from_array(pred)
     for s, t in [(4, 0), (3, 0), (0, 3), (7, 2), (1, 9), (18, 0)]:
         w, h = 1 << O.TX_W_LOG2[s], 1 << O.TX_H_LOG2[s]
         jobs = np.array([(0, 0, 3, 5), (140 - w, 140 - h, 0, 0)], dtype=R.TX_JOB)
-        got = R.diff_fwd_txfm_batch(ps, pp, jobs, s, t, 8)
+        got = R.diff_fwd_txfm_batch(ps, pp, jobs, s, t, bd)
         for k, j in enumerate(jobs):
             res = src[j["src_y"]:j["src_y"] + h, j["src_x"]:j["src_x"] + w].astype(np.int16) - \
                 pred[j["pred_y"]:j["pred_y"] + h, j["pred_x"]:j["pred_x"] + w].astype(np.int16)
-            np.testing.assert_array_equal(got[k], O.fwd_txfm2d(res, s, t, 8))
+            np.testing.assert_array_equal(got[k], O.fwd_txfm2d(res, s, t, bd),
+                                          err_msg=str((s, t, k)))
 
 
 # ---- motion search --------------------------------------------------------
