@@ -362,6 +362,72 @@ int rv_cfl_alpha_search_batch(const rv_plane *rec, const rv_plane *src, const rv
                               int n, int bsize, int bit_depth, int16_t *d_alpha,
                               uint64_t *d_cost, void *stream);
 
+/* ---- intra edges and mode screening for any block size (src/partition.rs:
+ * 500-693, src/recon_intra.rs:174-243, 376-458, src/rdo.rs:1008-1127) -------
+ * The front of rdo_mode_decision's intra path.  A tile is its luma rectangle
+ * in the planes' visible pixels; a plane's region of it is the rectangle
+ * decimated by the plane's xdec / ydec (TileRect::decimated).  A job names a
+ * transform block as get_intra_edges takes it: the tile, partition_bo
+ * (bo_x, bo_y: tile-relative, 4x4 luma units), the transform block's index
+ * (bx, by) inside the partition in units of tx_size, and po (po_x, po_y), the
+ * block's tile-relative pixel offset in the plane as the caller computed it
+ * (partition_bo.plane_offset() plus the transform block's offset).  cdf_off
+ * is read by the screening only.  Superblocks are 64x64.
+ *
+ * bsize: the partition BlockSize, one of the squares 4x4 .. 64x64 and the
+ * 2:1 / 1:2 sizes 4x8 .. 64x32; RV_ENOTSUP for the 4:1 / 1:4 sizes and
+ * anything above 64x64.  RV_EINVAL, before any launch, for a value that is
+ * no BlockSize / TxSize, a tx_size larger than the partition's block in the
+ * plane (after supersample_chroma_bsize, :459-498), a bit depth other than
+ * 8 / 10 / 12 or one the plane's pixel type does not hold, a subsampling
+ * other than 4:4:4 / 4:2:2 / 4:2:0, and null pointers.  The jobs being
+ * device data, the reference's own preconditions are the caller's: po inside
+ * the tile's region with the whole transform block (the reference would
+ * index out of the region), the region inside the plane's allocation.  A job
+ * that breaks one reads no pixel and yields zeros. */
+typedef struct rv_intra_tile {
+  int32_t x, y, width, height; /* luma pixels */
+} rv_intra_tile;
+typedef struct rv_intra_blk_job {
+  int32_t tile;
+  int32_t bo_x, bo_y;
+  int32_t bx, by;
+  int32_t po_x, po_y;
+  int32_t cdf_off;
+} rv_intra_blk_job;
+/* get_intra_edges (src/partition.rs:500-693) of every job from `plane` (any
+ * plane of the reconstruction; xdec / ydec are the plane's): have_top /
+ * have_left with the `> 1` rule of decimated planes, right / bottom
+ * availability against the tile's region, has_top_right / has_bottom_left,
+ * num_avail clipping and replication, and under opt_mode (-1: None, else a
+ * PredictionMode 0 .. 13, 13 UV_CFL_PRED) the PAETH demotion and the needs_*
+ * masks.  d_edges: [n][4 * 64 + 1] pixels of the plane's type in
+ * rv_predict_intra_batch's layout; entries no branch of the reference writes
+ * are zero. */
+int rv_intra_edges_batch(const rv_plane *plane, const rv_intra_tile *d_tiles, int n_tiles,
+                         const rv_intra_blk_job *d_jobs, int n, int bsize, int tx_size,
+                         int bit_depth, int opt_mode, void *d_edges, void *stream);
+/* The fused intra-mode screening (src/rdo.rs:1029-1127) of n luma blocks of
+ * one bsize (bsize.tx_size().block_size() == bsize: the 13 sizes above), in
+ * one launch.  Per job (bx = by = 0, po = 4 * bo): get_intra_edges(.., None)
+ * of rec; the 13 RAV1E_INTRA_MODES (src/predict.rs:32-46) predicted at
+ * bsize.tx_size() with the block's PredictionVariant and their get_satd
+ * against src (src/dist.rs:197-328); the stable sort by SATD; the stable
+ * descending sort by probability d = z - a (z from 32768) over the first 13
+ * entries of the CDF row d_cdf + cdf_off (a kf_y_cdf or y_mode_cdf row of the
+ * combined table rv_ec_default_cdf_all lays out, default or adapted; cdf_len:
+ * the table's length in entries); modes = the num_modes_rdo / 2 most
+ * probable, then the num_modes_rdo lowest SATDs not yet present, truncated to
+ * num_modes_rdo, which is 3 or 7 (RV_EINVAL otherwise).
+ * d_modes[i * 8]: the count, then up to 7 PredictionModes, zero-filled.
+ * d_satd (may be NULL): [n][13] in RAV1E_INTRA_MODES' order.  d_edges (may be
+ * NULL): as rv_intra_edges_batch writes them.  The reference predicts into
+ * rec and overwrites it later; rec is left untouched here. */
+int rv_intra_screen_batch(const rv_plane *rec, const rv_plane *src, const rv_intra_tile *d_tiles,
+                          int n_tiles, const rv_intra_blk_job *d_jobs, int n, int bsize,
+                          int bit_depth, const uint16_t *d_cdf, int cdf_len, int num_modes_rdo,
+                          uint8_t *d_modes, uint32_t *d_satd, void *d_edges, void *stream);
+
 /* ---- scene-change detection (src/scenechange/mod.rs) ---------------------
  * The frame-pair sums has_scenecut (:167-207) folds over Frame::iter()
  * (PixelIter, src/frame/mod.rs:126-172), before its division by len: for

@@ -266,6 +266,9 @@ def _declare(L):
         "rv_cdef_moments_batch": (i32, [P, P, vp, i32, i32, i32, vp, vp]),
         "rv_put_8tap_batch": (i32, [P, P, vp, i32, i32, i32, i32, i32, i32, vp]),
         "rv_predict_intra_batch": (i32, [P, vp, vp, i32, i32, i32, vp]),
+        "rv_intra_edges_batch": (i32, [P, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
+        "rv_intra_screen_batch": (i32, [P, P, vp, i32, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp,
+                                        vp]),
         "rv_cfl_luma_ac_batch": (i32, [P, vp, i32, i32, i32, i32, vp, vp]),
         "rv_predict_cfl_batch": (i32, [P, vp, vp, vp, vp, i32, i32, i32, vp]),
         "rv_cfl_alpha_search_batch": (i32, [P, P, vp, i32, i32, i32, vp, vp, vp]),
@@ -655,6 +658,165 @@ def predict_intra_batch(dst: DevicePlane, jobs, edges: np.ndarray, tx_size, bit_
     _check(lib().rv_predict_intra_batch(C.byref(dst.desc), dj.ptr, de.ptr, len(jobs), tx_size,
                                         bit_depth, None), "rv_predict_intra_batch")
     _sync()
+
+
+# ---- intra edges and mode screening (rv_intra_screen.hip) -------------------
+INTRA_TILE = np.dtype([("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4")])
+INTRA_BLK_JOB = np.dtype([("tile", "<i4"), ("bo_x", "<i4"), ("bo_y", "<i4"), ("bx", "<i4"),
+                          ("by", "<i4"), ("po_x", "<i4"), ("po_y", "<i4"), ("cdf_off", "<i4")])
+FRAME_TYPE_KEY, FRAME_TYPE_INTER = 0, 1  # FrameType (src/api/util.rs)
+# kf_y_cdf [5][5][14] and y_mode_cdf [4][14] in the combined mode table
+# (RV_ECM_KF_Y / RV_ECM_Y_MODE of rv_ec_mode_tables.h; tests/test_intra_screen.py
+# holds them to the header)
+ECM_KF_Y, ECM_Y_MODE = 4537, 4887
+_INTRA_MODE_CONTEXT = [0, 1, 2, 3, 4, 4, 4, 4, 3, 0, 1, 2, 0]  # src/context.rs:2206-2207
+_SIZE_GROUP = [0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3, 3, 3, 3, 0, 0, 1, 1, 2, 2]  # :206-207
+INTRA_MAX_BSIZE = BlockSize.BLOCK_64X64  # and no 4:1 / 1:4 size (all above it in the enum)
+# BlockSize::tx_size (src/partition.rs:199-230) of the sizes screened: the
+# transform of the block's own shape
+_BSIZE_TX = {int(b): TxSize["TX_" + b.name[6:]] for b in BlockSize if b <= BlockSize.BLOCK_64X64}
+
+
+def intra_mode_cdf_offset(frame_type, bsize, above_mode=0, left_mode=0) -> int:
+    """Offset, in the combined CDF table, of the row rdo_mode_decision takes
+    the intra-mode probabilities from (src/rdo.rs:1090-1094): for an INTER
+    frame get_cdf_intra_mode(bsize) = y_mode_cdf[size_group_lookup[bsize]],
+    else get_cdf_intra_mode_kf = kf_y_cdf[above_ctx][left_ctx] of the above /
+    left blocks' modes, DC_PRED where the tile has none (src/context.rs:
+    2203-2248)."""
+    if frame_type == FRAME_TYPE_INTER:
+        return ECM_Y_MODE + 14 * _SIZE_GROUP[int(BlockSize(bsize))]
+    for m in (above_mode, left_mode):
+        if not 0 <= int(m) <= 12:
+            raise Rav1eHipError("intra_mode_cdf_offset: a key frame's neighbours are intra blocks "
+                                "(modes 0 .. 12)")
+    return ECM_KF_Y + (_INTRA_MODE_CONTEXT[int(above_mode)] * 5 +
+                       _INTRA_MODE_CONTEXT[int(left_mode)]) * 14
+
+
+def intra_plane_offset(bo_x, bo_y, xdec=0, ydec=0, bx=0, by=0, tx_size=TxSize.TX_4X4):
+    """po of transform block (bx, by) of the partition at block offset (bo_x,
+    bo_y): BlockOffset::plane_offset (src/context.rs:1293-1298), (bo >> dec)
+    << 2 per axis, plus the transform block's own offset bx * tx width, by *
+    tx height, as the encoder's transform loops form it."""
+    tx = TxSize(tx_size)
+    return ((np.asarray(bo_x) >> xdec) << 2) + np.asarray(bx) * tx.width(), \
+           ((np.asarray(bo_y) >> ydec) << 2) + np.asarray(by) * tx.height()
+
+
+def _intra_blk_args(who, plane: DevicePlane, tiles, jobs, bsize, tx_size, bit_depth):
+    """The checks rv_intra_screen.hip leaves to the caller because jobs and
+    tiles are device data: the reference would index outside its region."""
+    tiles = np.ascontiguousarray(tiles, dtype=INTRA_TILE).reshape(-1)
+    jobs = np.ascontiguousarray(jobs, dtype=INTRA_BLK_JOB).reshape(-1)
+    d = plane.desc
+    n = len(jobs)
+    # the argument checks are the library's (bad sizes return their code
+    # without a launch); only what depends on the records is checked here
+    b, t = int(bsize), int(tx_size)
+    if n and 0 <= b <= int(INTRA_MAX_BSIZE) and 0 <= t <= 18 and len(tiles):
+        tx = TxSize(t)
+        if ((jobs["tile"] < 0) | (jobs["tile"] >= len(tiles))).any():
+            raise Rav1eHipError(f"{who}: a job names no tile")
+        tl = tiles[jobs["tile"]]
+        rx, ry = tl["x"] >> d.xdec, tl["y"] >> d.ydec
+        rw, rh = tl["width"] >> d.xdec, tl["height"] >> d.ydec
+        if (tl["x"] < 0).any() or (tl["y"] < 0).any() or (rw <= 0).any() or (rh <= 0).any() or \
+                not _inside(plane, rx, ry, rx + rw, ry + rh):
+            raise Rav1eHipError(f"{who}: a tile's region leaves the plane")
+        if any((jobs[f] < 0).any() for f in ("bo_x", "bo_y", "bx", "by", "po_x", "po_y")):
+            raise Rav1eHipError(f"{who}: negative block offset, index or plane offset")
+        if (jobs["po_x"] + tx.width() > rw).any() or (jobs["po_y"] + tx.height() > rh).any():
+            raise Rav1eHipError(f"{who}: a transform block leaves its tile's region "
+                                "(get_intra_edges would index outside it)")
+    return tiles, jobs
+
+
+def intra_edges_batch(plane: DevicePlane, tiles, jobs, bsize, tx_size, bit_depth=8,
+                      opt_mode=None) -> np.ndarray:
+    """get_intra_edges (src/partition.rs:500-693) of every job (INTRA_BLK_JOB)
+    from one plane of the reconstruction: tiles (INTRA_TILE) are luma
+    rectangles, bsize the partition, tx_size the transform block, opt_mode
+    None or a PredictionMode (UV_CFL_PRED included).  Returns (n, 257) pixels
+    in predict_intra_batch's layout; what the reference leaves unwritten is
+    zero."""
+    tiles, jobs = _intra_blk_args("intra_edges_batch", plane, tiles, jobs, bsize, tx_size,
+                                  bit_depth)
+    n = len(jobs)
+    dt, dj = DeviceBuffer.from_array(tiles), DeviceBuffer.from_array(jobs)
+    out = DeviceBuffer(EDGE_PX * np.dtype(plane.dtype).itemsize * max(1, n))
+    _check(lib().rv_intra_edges_batch(C.byref(plane.desc), dt.ptr, len(tiles), dj.ptr, n,
+                                      int(bsize), int(tx_size), bit_depth,
+                                      -1 if opt_mode is None else int(opt_mode), out.ptr, None),
+           "rv_intra_edges_batch")
+    _sync()
+    return out.download(plane.dtype, EDGE_PX * n).reshape(n, EDGE_PX)
+
+
+def intra_mode_screen_batch(rec: DevicePlane, src: DevicePlane, tiles, jobs, bsize, cdf,
+                            num_modes_rdo, bit_depth=8, with_satd=False, with_edges=False):
+    """The intra-mode screening of rdo_mode_decision (src/rdo.rs:1029-1127)
+    for n luma blocks of one bsize in one launch: rec / src the luma planes of
+    the reconstruction and the source, jobs INTRA_BLK_JOB with bx = by = 0,
+    po = 4 * bo and cdf_off the job's row in cdf (a u16 array or a
+    DeviceBuffer holding the combined table; intra_mode_cdf_offset).
+    Returns the list of mode lists and, on request, the SATDs (n, 13) in
+    RAV1E_INTRA_MODES' order and the edges (n, 257).  rec is not written."""
+    who = "intra_mode_screen_batch"
+    b = int(bsize)
+    tx = _BSIZE_TX.get(b, TxSize.TX_4X4)
+    tiles, jobs = _intra_blk_args(who, rec, tiles, jobs, bsize, tx, bit_depth)
+    n = len(jobs)
+    if isinstance(cdf, DeviceBuffer):
+        dc, cdf_len = cdf, cdf.nbytes // 2
+    else:
+        cdf = np.ascontiguousarray(cdf, dtype=np.uint16).reshape(-1)
+        dc, cdf_len = DeviceBuffer.from_array(cdf), len(cdf)
+    if n and b in _BSIZE_TX and len(tiles):
+        if (jobs["bx"] != 0).any() or (jobs["by"] != 0).any() or \
+                (jobs["po_x"] != 4 * jobs["bo_x"]).any() or (jobs["po_y"] != 4 * jobs["bo_y"]).any():
+            raise Rav1eHipError(f"{who}: the screening is of the whole luma block (bx = by = 0, "
+                                "po = 4 * bo)")
+        tl = tiles[jobs["tile"]]
+        sx, sy = tl["x"] + jobs["po_x"], tl["y"] + jobs["po_y"]
+        if not _inside(src, sx, sy, sx + tx.width(), sy + tx.height()):
+            raise Rav1eHipError(f"{who}: a source block leaves the padded plane")
+        if (jobs["cdf_off"] < 0).any() or (jobs["cdf_off"] + 14 > cdf_len).any():
+            raise Rav1eHipError(f"{who}: a CDF row leaves the table")
+    dt, dj = DeviceBuffer.from_array(tiles), DeviceBuffer.from_array(jobs)
+    dm = DeviceBuffer(8 * max(1, n))
+    ds = DeviceBuffer(4 * 13 * max(1, n)) if with_satd else None
+    de = DeviceBuffer(EDGE_PX * np.dtype(rec.dtype).itemsize * max(1, n)) if with_edges else None
+    _check(lib().rv_intra_screen_batch(C.byref(rec.desc), C.byref(src.desc), dt.ptr, len(tiles),
+                                       dj.ptr, n, b, bit_depth, dc.ptr, cdf_len,
+                                       int(num_modes_rdo), dm.ptr, ds.ptr if ds else None,
+                                       de.ptr if de else None, None), "rv_intra_screen_batch")
+    _sync()
+    m = dm.download(np.uint8, 8 * n).reshape(n, 8)
+    res = [[int(v) for v in row[1:1 + row[0]]] for row in m]
+    out = (res,)
+    if with_satd:
+        out += (ds.download(np.uint32, 13 * n).reshape(n, 13),)
+    if with_edges:
+        out += (de.download(rec.dtype, EDGE_PX * n).reshape(n, EDGE_PX),)
+    return out[0] if len(out) == 1 else out
+
+
+def intra_screen_select(satds, cdf_row, num_modes_rdo):
+    """The host form of the selection (src/rdo.rs:1086-1127) for one block:
+    satds in RAV1E_INTRA_MODES' order, cdf_row the row's entries.  What
+    intra_mode_screen_batch does on the device after its SATDs."""
+    order = sorted(range(13), key=lambda k: int(satds[k]))  # stable
+    z, probs_all = 32768, []
+    for a in list(cdf_row)[:13]:
+        probs_all.append((z - int(a)) & 0xffff)
+        z = int(a)
+    porder = sorted(range(13), key=lambda k: 0xffff ^ probs_all[RAV1E_INTRA_MODES[k]])
+    modes = [RAV1E_INTRA_MODES[k] for k in porder[:num_modes_rdo // 2]]
+    for k in order[:num_modes_rdo]:
+        if RAV1E_INTRA_MODES[k] not in modes:
+            modes.append(RAV1E_INTRA_MODES[k])
+    return modes[:num_modes_rdo]
 
 
 # ---- chroma from luma (rv_cfl.hip) ------------------------------------------

@@ -177,4 +177,180 @@ __device__ __forceinline__ void intra_edges_sb(const rv_plane &p, int tx, int ty
   }
 }
 
+// ---- get_intra_edges, general form (src/partition.rs:500-693) --------------
+// BlockSize (src/partition.rs:116-140) in 4x4 units; 0 past BLOCK_64X64 and
+// for the 4:1 / 1:4 sizes, which the general form does not take.
+static __constant__ uint8_t kBlkW4[22] = {1, 1, 2, 2, 2, 4, 4, 4, 8, 8, 8, 16, 16, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static __constant__ uint8_t kBlkH4[22] = {1, 2, 1, 2, 4, 2, 4, 8, 4, 8, 16, 8, 16, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// The general case of has_top_right / has_bottom_left (src/recon_intra.rs:
+// 233-241, 448-456): whether the block of the same size to the top right /
+// bottom left of the bw4 x bh4 block at (mi_row, mi_col) of a 64x64
+// superblock is coded before it.  Blocks are coded in the recursive
+// top-left, top-right, bottom-left, bottom-right order; a 2:1 block is the
+// top / bottom half and a 1:2 block the left / right half of the square s =
+// max(bw4, bh4).  Walking up the quadtree from that square:
+//   top right:   a bottom-left quadrant sees its top-right sibling, a
+//                bottom-right one would need the next square to the right, a
+//                top-left one the square above; a top-right one asks its
+//                parent.
+//   bottom left: a top-left quadrant sees the square to its left, a right
+//                quadrant would need its own bottom-left sibling, coded
+//                later; a bottom-left one asks its parent.
+// The reference reads the same answers from tables indexed by position.
+__device__ __forceinline__ bool intra_tr_coded(int mi_row, int mi_col, int bw4, int bh4) {
+  const int r = mi_row & 15, c = mi_col & 15;
+  if (bw4 > bh4 && (r & bh4)) return false;  // bottom half: the square to the right
+  if (bw4 < bh4 && !(c & bw4)) return true;  // left half: above the right half
+  for (int s = bw4 > bh4 ? bw4 : bh4; s < 16; s <<= 1) {
+    if (r & s) return !(c & s);
+    if (!(c & s)) return true;
+  }
+  return true;  // the superblock's top row
+}
+__device__ __forceinline__ bool intra_bl_coded(int mi_row, int mi_col, int bw4, int bh4) {
+  const int r = mi_row & 15, c = mi_col & 15;
+  if (bw4 > bh4 && !(r & bh4)) return true;  // top half: beside the square to the left
+  if (bw4 < bh4 && (c & bw4)) return false;  // right half: below the left half
+  for (int s = bw4 > bh4 ? bw4 : bh4; s < 16; s <<= 1) {
+    if (c & s) return false;
+    if (!(r & s)) return true;
+  }
+  return false;  // the superblock's bottom row
+}
+
+// has_top_right (src/recon_intra.rs:174-243), 64x64 superblocks.  bw4 / bh4:
+// the partition after supersample_chroma_bsize; txw4: tx_size.width_mi().
+__device__ __forceinline__ bool intra_has_top_right(int bw4, int bh4, int mi_col, int mi_row,
+                                                    bool top, bool right, int txw4, int row_off,
+                                                    int col_off, int ss_x) {
+  if (!top || !right) return false;
+  const int plane_bw = max(bw4 >> ss_x, 1);
+  if (row_off > 0) return col_off + txw4 < plane_bw;
+  if (col_off + txw4 < plane_bw) return true;
+  const int lw = 31 - __builtin_clz(bw4), lh = 31 - __builtin_clz(bh4);
+  const int br = (mi_row & 15) >> lh, bc = (mi_col & 15) >> lw;
+  if (br == 0) return true;
+  if (((bc + 1) << lw) >= 16) return false;
+  return intra_tr_coded(mi_row, mi_col, bw4, bh4);
+}
+
+// has_bottom_left (src/recon_intra.rs:376-458), 64x64 superblocks.
+__device__ __forceinline__ bool intra_has_bottom_left(int bw4, int bh4, int mi_col, int mi_row,
+                                                      bool bottom, bool left, int txh4,
+                                                      int row_off, int col_off, int ss_y) {
+  if (!bottom || !left) return false;
+  if (col_off > 0) return false;
+  const int plane_bh = max(bh4 >> ss_y, 1);
+  if (row_off + txh4 < plane_bh) return true;
+  const int lw = 31 - __builtin_clz(bw4), lh = 31 - __builtin_clz(bh4);
+  const int br = (mi_row & 15) >> lh, bc = (mi_col & 15) >> lw;
+  if (bc == 0) return ((br << lh) >> ss_y) + row_off + txh4 < (16 >> ss_y);
+  if (((br + 1) << lh) >= 16) return false;
+  return intra_bl_coded(mi_row, mi_col, bw4, bh4);
+}
+
+// supersample_chroma_bsize (src/partition.rs:459-498) on 4x4-unit sizes: a
+// 4-pixel side doubles on a decimated axis.  Of the sizes taken here only
+// 4x4, 4x8 and 8x4 change.
+__device__ __forceinline__ void intra_supersample(int &bw4, int &bh4, int ss_x, int ss_y) {
+  const int w = bw4, h = bh4;
+  if (w == 1 && h == 1) {
+    bw4 <<= ss_x;
+    bh4 <<= ss_y;
+  } else if (w == 1 && h == 2) {  // BLOCK_4X8 -> 8X8 where x is decimated
+    bw4 <<= ss_x;
+  } else if (w == 2 && h == 1) {  // BLOCK_8X4 -> 8X8 where y is decimated
+    bh4 <<= ss_y;
+  }
+}
+
+// What one call of get_intra_edges depends on besides the pixels.
+struct IntraEdgeGeo {
+  int tx, ty, tw, th;  // the tile's region of this plane: origin (plane pixels) and size
+  int x, y;            // po: the block's tile-relative pixel offset in this plane
+  int w, h;            // tx_size
+  int ntr, nbl;        // num_avail of the top-right / bottom-left branch
+  uint32_t needs;      // bit 0 left, 1 top-left, 2 top, 3 top-right, 4 bottom-left
+};
+
+// The needs_* masks under opt_mode (src/partition.rs:525-557); mode < 0: None.
+__device__ __forceinline__ uint32_t intra_edge_needs(int mode, int x, int y) {
+  if (mode < 0) return 31u;
+  if (mode == 12) mode = x == 0 && y == 0 ? 0 : y == 0 ? 2 : x == 0 ? 1 : 12;
+  const bool dc_or_cfl = mode == 0 || mode == 13;
+  const bool left = mode != 1 && (!dc_or_cfl || x != 0) && !(mode == 3 || mode == 8);
+  const bool topleft = mode == 12 || mode == 5 || mode == 4 || mode == 6;
+  const bool top = mode != 2 && (!dc_or_cfl || y != 0);
+  const bool topright = mode == 3 || mode == 8;
+  const bool bottomleft = mode == 7;
+  return (uint32_t)left | (uint32_t)topleft << 1 | (uint32_t)top << 2 | (uint32_t)topright << 3 |
+         (uint32_t)bottomleft << 4;
+}
+
+// The geometry of get_intra_edges (src/partition.rs:597-674) for transform
+// block (bx, by) of the partition at (mi_col, mi_row) (tile-relative 4x4
+// units) of size bw4 x bh4 (before supersample_chroma_bsize).
+__device__ __forceinline__ IntraEdgeGeo intra_edge_geo(int tx, int ty, int tw, int th, int mi_col,
+                                                       int mi_row, int bw4, int bh4, int bx, int by,
+                                                       int x, int y, int w, int h, int xdec,
+                                                       int ydec, int mode) {
+  IntraEdgeGeo g;
+  g.tx = tx, g.ty = ty, g.tw = tw, g.th = th, g.x = x, g.y = y, g.w = w, g.h = h;
+  g.needs = intra_edge_needs(mode, x, y);
+  const int bx4 = bx * (w >> 2), by4 = by * (h >> 2);
+  const bool have_top = by4 != 0 || mi_row > (ydec ? 1 : 0);
+  const bool have_left = bx4 != 0 || mi_col > (xdec ? 1 : 0);
+  const bool right = x + w < tw, bottom = y + h < th;
+  intra_supersample(bw4, bh4, xdec, ydec);
+  g.ntr = (y != 0 && intra_has_top_right(bw4, bh4, mi_col, mi_row, have_top, right, w >> 2, by4,
+                                         bx4, xdec))
+              ? min(w, tw - x - w) : 0;
+  g.nbl = (x != 0 && intra_has_bottom_left(bw4, bh4, mi_col, mi_row, bottom, have_left, h >> 2,
+                                           by4, bx4, ydec))
+              ? min(h, th - y - h) : 0;
+  return g;
+}
+
+// Entry i of edge_buf (src/partition.rs:559-690); entries no branch writes
+// are zero.  Each entry is computed from the plane alone, so any lane may
+// produce any entry.
+template <typename Px>
+__device__ __forceinline__ int32_t intra_edge_px(const rv_plane &p, const IntraEdgeGeo &g, int bd,
+                                                 int i) {
+  const int base = 128 << (bd - 8);
+  const int L = 128, A = 129;
+  const int x = g.x, y = g.y, w = g.w, h = g.h;
+  auto D = [&](int r, int c) -> int32_t { return (int32_t)*plane_ptr<Px>(p, g.tx + c, g.ty + r); };
+  auto left = [&](int k) -> int32_t {  // left[2 * MAX_TX_SIZE - h + k]
+    return x != 0 ? D(y + h - 1 - k, x - 1) : (y != 0 ? D(y - 1, 0) : base + 1);
+  };
+  auto above = [&](int k) -> int32_t {  // above[k], k < w
+    return y != 0 ? D(y - 1, x + k) : (x != 0 ? D(0, x - 1) : base - 1);
+  };
+  if (i >= L - h && i < L) return (g.needs & 1) ? left(i - (L - h)) : 0;
+  if (i == L)
+    return (g.needs & 2) ? (x == 0 && y == 0 ? base : y == 0 ? D(0, x - 1) : x == 0 ? D(y - 1, 0)
+                                                                                   : D(y - 1, x - 1))
+                         : 0;
+  if (i >= A && i < A + w) return (g.needs & 4) ? above(i - A) : 0;
+  // top-right: num_avail pixels (up to w, which may exceed h), then the last
+  // one up to h
+  if (i >= A + w && i < A + w + max(h, g.ntr)) {
+    if (!(g.needs & 8)) return 0;
+    const int k = i - A - w;
+    if (k < g.ntr) return D(y - 1, x + w + k);
+    if (g.ntr > 0) return D(y - 1, x + w + g.ntr - 1);
+    return (g.needs & 4) ? above(w - 1) : 0;  // above[w - 1] as the top branch left it
+  }
+  if (i >= L - h - max(w, g.nbl) && i < L - h) {  // bottom-left: likewise, downwards
+    if (!(g.needs & 16)) return 0;
+    const int k = L - h - 1 - i;
+    if (k < g.nbl) return D(y + h + k, x - 1);
+    if (g.nbl > 0) return D(y + h + g.nbl - 1, x - 1);
+    return (g.needs & 1) ? left(0) : 0;  // left[2 * MAX_TX_SIZE - h] as the left branch left it
+  }
+  return 0;
+}
+
 }  // namespace rv
