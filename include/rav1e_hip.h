@@ -428,6 +428,122 @@ int rv_intra_screen_batch(const rv_plane *rec, const rv_plane *src, const rv_int
                           int bit_depth, const uint16_t *d_cdf, int cdf_len, int num_modes_rdo,
                           uint8_t *d_modes, uint32_t *d_satd, void *d_edges, void *stream);
 
+/* ---- a partition's transform blocks as one RDO candidate ------------------
+ * write_tx_blocks (src/encoder.rs:1757-1903, intra) and write_tx_tree
+ * (:1907-2037, inter) without the bitstream writer: every encode_tx_block
+ * (:1077-1237) of the partition, for a batch of independent jobs in one
+ * launch.  A job is one partition at (bo_x, bo_y) (tile-relative 4x4 luma
+ * units, a multiple of the partition's size) of a tile (rv_intra_tile), coded
+ * with its own qindex (get_qidx is per block, 1 .. 255) and CfL alphas.  What
+ * is the same for a whole candidate pass is a launch parameter: the partition
+ * and luma transform size, the modes, the transform type, skip.
+ *
+ * The transform blocks run in the reference's order: luma by outer / bx
+ * inner, then U, then V.  Each does what encode_tx_block does:
+ *  1. intra only: get_intra_edges(rec, partition_bo, bx, by, bsize, po,
+ *     tx_size, bd, Some(mode)) (src/partition.rs:500-693) and predict_intra;
+ *     UV_CFL_PRED with the job's alpha.  Edge pixels inside the partition come
+ *     from the job's own working copy, as its earlier transform blocks left
+ *     it; pixels outside from rec, which is never written, so several
+ *     candidates at one position are independent.
+ *  2. skip ends the block here (:1140-1142); an inter skip job does nothing
+ *     at all (:1914-1916).
+ *  3. diff against src, forward transform, QuantizationContext::update +
+ *     quantize, dequantize.  The quantizer's arguments are the reference's:
+ *     luma is_intra = luma_mode.is_intra(), dc_delta_q[0], ac delta 0
+ *     (:1774-1781, :1925-1932); chroma is_intra = true in write_tx_blocks
+ *     (:1853-1860) and false in write_tx_tree (:1987-1994), with
+ *     dc_delta_q[p] / ac_delta_q[p]; dequantize takes dc_delta_q[p] /
+ *     ac_delta_q[p] for every plane (:1192-1200).
+ *  4. inverse transform + add only when need_recon_pixel
+ *     (use_tx_domain_distortion is true at every preset, :1204-1209);
+ *     otherwise the working copy keeps the bare prediction, and later blocks
+ *     of the plane predict from it, as in the reference (4:4:4 and 4:2:2
+ *     64x64 chroma).
+ *  5. the tx-domain distortion: the squared difference of coeffs and rcoeffs
+ *     over the coded area, rounded by 2 * (3 - get_log_tx_scale) bits
+ *     (:1210-1224).
+ * Chroma: uv_tx_size = bsize.largest_chroma_tx_size(xdec, ydec) (src/
+ * partition.rs:288-297); bw_uv / bh_uv and po as :1821-1832, :1871-1873.
+ * Intra chroma type: uv_intra_mode_to_tx_type_context(chroma_mode), DCT_DCT
+ * when a side of uv_tx_size is >= 32 (:1846-1850).  Inter chroma type:
+ * tx_type if the luma block has_coeff, else DCT_DCT (:1984), has_coeff being
+ * eob != 0 when need_recon_pixel || coeff_rate (write_coeffs_lv_map's return,
+ * src/context.rs:4002-4005) and true otherwise (:1173-1189); coeff_rate
+ * stands for rdo_type.needs_coeff_rate().  luma_ac is taken after the luma
+ * blocks (:1834-1836) from what the luma working copy then holds.  An inter
+ * launch (luma_mode >= NEARESTMV) takes the prediction from `pred`, as
+ * motion_compensate left it; chroma_mode is not read.
+ *
+ * bsize: 8x8 .. 64x64 and the 2:1 / 1:2 sizes 8x16 .. 64x32.  tx_size: any
+ * TxSize no larger than bsize on either side.  4:2:0, 4:2:2, 4:4:4 (the
+ * chroma planes' xdec / ydec); 8 / 10 / 12 bit.
+ * RV_ENOTSUP, before any launch: 4xN / Nx4 partitions, the 4:1 / 1:4 sizes
+ * and sizes above 64x64; a (bsize, layout) without a subsampled_size (8x16,
+ * 16x32, 32x64 at 4:2:2; the reference panics); a transform type the forward
+ * transform -- or, with need_recon_pixel, the inverse -- does not implement
+ * for the size.  RV_EINVAL, before any launch: values that are no BlockSize /
+ * TxSize / TxType / mode; a tx_size larger than bsize; an inter launch whose
+ * tx_size.block_size() != bsize; intra luma blocks smaller than the partition
+ * without need_recon_pixel (encode_tx_block's debug_assert, :1111-1113); CfL
+ * with bsize above 32x32; a type other than DCT_DCT on a 64-point size; null
+ * pointers; a bit depth other than 8 / 10 / 12 or one the planes' pixel type
+ * does not hold; plane sets of different subsampling; dst planes that overlap
+ * rec.  Jobs are device data, so the per-job preconditions are the caller's,
+ * as for rv_intra_edges_batch: the tile's regions inside every plane's
+ * allocation, the partition aligned and inside its tile, qindex in 1 .. 255.
+ * A job that breaks one reads no pixel, yields zeros and writes no dst.
+ *
+ * Outputs, per job (rv_tx_blocks_layout gives the strides and offsets):
+ * d_levels[n][levels_per_job], the quantized levels of every transform block
+ * over its coded area in the raster rv_quantize_batch writes (the input of
+ * rv_ec_cand_tokenize); d_eob[n][blocks_per_job], one past the last non-zero
+ * level in scan order (write_coeffs_lv_map's eob); d_dist[n][blocks_per_job],
+ * the shifted tx distortion.  All three are zero for a skip job.  dst (may be
+ * NULL): planes that receive the partition's pixels of every coded plane --
+ * the reconstruction, or the prediction without need_recon_pixel or under
+ * skip; an inter skip job writes nothing.  compute_distortion_bias,
+ * dist_scale and estimate_rate (rv_estimate_rate_batch) stay with the
+ * caller. */
+typedef struct rv_tx_blocks_params {
+  int32_t bsize, tx_size, tx_type;
+  int32_t luma_mode, chroma_mode; /* PredictionMode; luma_mode >= 14: inter */
+  int32_t skip, luma_only, need_recon_pixel, coeff_rate;
+  int32_t bit_depth;
+  int32_t dc_delta_q[3], ac_delta_q[3];
+} rv_tx_blocks_params;
+typedef struct rv_tx_blocks_job {
+  int32_t tile;
+  int32_t bo_x, bo_y;
+  int32_t qindex;
+  int32_t alpha_u, alpha_v; /* CFLParams::alpha(0 / 1), read under UV_CFL_PRED */
+} rv_tx_blocks_job;
+#define RV_TX_BLOCKS_MAX 256 /* transform blocks of a plane: 64x64 in TX_4X4 */
+typedef struct rv_tx_blocks_layout_t {
+  int32_t planes;          /* 1 with luma_only, else 3 */
+  int32_t tx_size[3];      /* tx_size, uv_tx_size, uv_tx_size */
+  int32_t plane_w[3], plane_h[3]; /* the partition's pixels in the plane */
+  int32_t cols[3], rows[3];       /* bw x bh, bw_uv x bh_uv */
+  int32_t n_blocks[3];
+  int32_t coded_area[3];   /* av1_get_coded_tx_size(tx_size).area() per block */
+  int32_t first_block[3];  /* the plane's first entry in a job's eob / dist */
+  int32_t level_off[3];    /* the plane's first level in a job's levels; block
+                              i of the plane follows at i * coded_area */
+  int32_t blocks_per_job, levels_per_job; /* the per-job strides */
+  /* pixel offset of block i (raster: by outer, bx inner) inside the partition */
+  uint8_t blk_x[3][RV_TX_BLOCKS_MAX], blk_y[3][RV_TX_BLOCKS_MAX];
+} rv_tx_blocks_layout_t;
+/* Pure host function: how a caller sizes and indexes the outputs.  Returns
+ * the launch's error codes for (bsize, tx_size, layout). */
+int rv_tx_blocks_layout(int bsize, int tx_size, int xdec, int ydec, int luma_only,
+                        rv_tx_blocks_layout_t *out);
+/* rec / src (and pred for an inter launch, dst when given): 3 planes each, 1
+ * with luma_only. */
+int rv_tx_blocks_batch(const rv_plane *rec, const rv_plane *src, const rv_plane *pred,
+                       const rv_plane *dst, const rv_intra_tile *d_tiles, int n_tiles,
+                       const rv_tx_blocks_job *d_jobs, int n, const rv_tx_blocks_params *params,
+                       int32_t *d_levels, uint32_t *d_eob, uint64_t *d_dist, void *stream);
+
 /* ---- scene-change detection (src/scenechange/mod.rs) ---------------------
  * The frame-pair sums has_scenecut (:167-207) folds over Frame::iter()
  * (PixelIter, src/frame/mod.rs:126-172), before its division by len: for

@@ -269,6 +269,8 @@ def _declare(L):
         "rv_intra_edges_batch": (i32, [P, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
         "rv_intra_screen_batch": (i32, [P, P, vp, i32, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp,
                                         vp]),
+        "rv_tx_blocks_layout": (i32, [i32, i32, i32, i32, i32, vp]),
+        "rv_tx_blocks_batch": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
         "rv_cfl_luma_ac_batch": (i32, [P, vp, i32, i32, i32, i32, vp, vp]),
         "rv_predict_cfl_batch": (i32, [P, vp, vp, vp, vp, i32, i32, i32, vp]),
         "rv_cfl_alpha_search_batch": (i32, [P, P, vp, i32, i32, i32, vp, vp, vp]),
@@ -817,6 +819,137 @@ def intra_screen_select(satds, cdf_row, num_modes_rdo):
         if RAV1E_INTRA_MODES[k] not in modes:
             modes.append(RAV1E_INTRA_MODES[k])
     return modes[:num_modes_rdo]
+
+
+# ---- a partition's transform blocks (rv_tx_blocks.hip) ----------------------
+TX_BLOCKS_JOB = np.dtype([("tile", "<i4"), ("bo_x", "<i4"), ("bo_y", "<i4"), ("qindex", "<i4"),
+                          ("alpha_u", "<i4"), ("alpha_v", "<i4")])
+TX_BLOCKS_MAX = 256  # RV_TX_BLOCKS_MAX
+
+
+class RvTxBlocksParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("bsize", "tx_size", "tx_type", "luma_mode", "chroma_mode",
+                                         "skip", "luma_only", "need_recon_pixel", "coeff_rate",
+                                         "bit_depth")] + \
+               [("dc_delta_q", C.c_int32 * 3), ("ac_delta_q", C.c_int32 * 3)]
+
+
+class RvTxBlocksLayout(C.Structure):
+    _fields_ = [("planes", C.c_int32)] + \
+               [(n, C.c_int32 * 3) for n in ("tx_size", "plane_w", "plane_h", "cols", "rows",
+                                             "n_blocks", "coded_area", "first_block", "level_off")] + \
+               [("blocks_per_job", C.c_int32), ("levels_per_job", C.c_int32),
+                ("blk_x", (C.c_uint8 * TX_BLOCKS_MAX) * 3), ("blk_y", (C.c_uint8 * TX_BLOCKS_MAX) * 3)]
+
+
+def tx_blocks_layout(bsize, tx_size, xdec=1, ydec=1, luma_only=False) -> RvTxBlocksLayout:
+    """rv_tx_blocks_layout: per plane the transform-block count (cols x rows =
+    bw x bh, bw_uv x bh_uv of src/encoder.rs:1764-1765, 1821-1832), the
+    plane's tx_size (uv_tx_size = largest_chroma_tx_size), the coded area per
+    block and each block's pixel offset inside the partition, and the per-job
+    strides of tx_blocks_batch's outputs.  Raises with the library's error
+    code (Rav1eHipError.code) for what the launch would refuse."""
+    out = RvTxBlocksLayout()
+    rc = lib().rv_tx_blocks_layout(int(bsize), int(tx_size), int(xdec), int(ydec),
+                                   1 if luma_only else 0, C.byref(out))
+    if rc != RV_OK:
+        err = Rav1eHipError(f"rv_tx_blocks_layout failed ({rc}): {lib().rv_last_error().decode()}")
+        err.code = rc
+        raise err
+    return out
+
+
+def _plane_set(planes, count):
+    if planes is None:
+        return None
+    arr = (RvPlane * 3)()
+    for p in range(count):
+        arr[p] = planes[p].desc
+    return arr
+
+
+def tx_blocks_batch(rec, src, tiles, jobs, bsize, tx_size, luma_mode, chroma_mode=0,
+                    tx_type=TxType.DCT_DCT, skip=False, luma_only=False, need_recon_pixel=True,
+                    coeff_rate=True, bit_depth=8, dc_delta_q=(0, 0, 0), ac_delta_q=(0, 0, 0),
+                    pred=None, dst=None):
+    """write_tx_blocks / write_tx_tree without the bitstream writer (src/
+    encoder.rs:1757-2037) for n partitions of one bsize in one launch: every
+    encode_tx_block of each job, in the reference's order.  rec / src (and
+    pred for an inter luma_mode, dst when the pixels are wanted): sequences of
+    three DevicePlanes (one with luma_only); tiles INTRA_TILE, jobs
+    TX_BLOCKS_JOB (tile, partition_bo in tile-relative 4x4 luma units, the
+    block's qindex, the CfL alphas).  rec is not written.
+
+    Returns (layout, levels, eobs, dists): three lists with one array per
+    coded plane, levels (n, n_blocks, coded_area) i32 in rv_quantize_batch's
+    raster, eobs (n, n_blocks) u32 as write_coeffs_lv_map counts them, dists
+    (n, n_blocks) u64 the shifted tx-domain distortion."""
+    who = "tx_blocks_batch"
+    tiles = np.ascontiguousarray(tiles, dtype=INTRA_TILE).reshape(-1)
+    jobs = np.ascontiguousarray(jobs, dtype=TX_BLOCKS_JOB).reshape(-1)
+    n = len(jobs)
+    count = 1 if luma_only else 3
+    inter = int(luma_mode) >= int(PredictionMode.NEARESTMV)
+    for name, ps in (("rec", rec), ("src", src), ("pred", pred), ("dst", dst)):
+        if ps is None and name in ("rec", "src"):
+            raise Rav1eHipError(f"{who}: {name} is required")
+        if ps is not None and len(ps) < count:
+            raise Rav1eHipError(f"{who}: {name} needs {count} plane(s)")
+    xdec, ydec = (0, 0) if luma_only else (rec[1].desc.xdec, rec[1].desc.ydec)
+    # the argument checks are the library's (they return their code without a
+    # launch); what depends on the records -- device data to the library -- is
+    # checked here: the reference would index outside its regions
+    b = int(bsize)
+    if n and 0 <= b <= int(INTRA_MAX_BSIZE):
+        bw4, bh4 = BlockSize(b).width() // 4, BlockSize(b).height() // 4
+        if len(tiles) == 0 or ((jobs["tile"] < 0) | (jobs["tile"] >= len(tiles))).any():
+            raise Rav1eHipError(f"{who}: a job names no tile")
+        tl = tiles[jobs["tile"]]
+        if (jobs["bo_x"] < 0).any() or (jobs["bo_y"] < 0).any() or (jobs["bo_x"] % bw4).any() or \
+                (jobs["bo_y"] % bh4).any():
+            raise Rav1eHipError(f"{who}: a partition offset is negative or not a multiple of the "
+                                "block size")
+        if (4 * (jobs["bo_x"] + bw4) > tl["width"]).any() or \
+                (4 * (jobs["bo_y"] + bh4) > tl["height"]).any():
+            raise Rav1eHipError(f"{who}: a partition leaves its tile")
+        if ((jobs["qindex"] < 1) | (jobs["qindex"] > 255)).any():
+            raise Rav1eHipError(f"{who}: qindex is 1 .. 255 (lossless is not supported)")
+        for name, ps in (("rec", rec), ("src", src), ("pred", pred if inter else None),
+                         ("dst", dst)):
+            for p in range(count if ps is not None else 0):
+                d = ps[p].desc
+                rx, ry = tl["x"] >> d.xdec, tl["y"] >> d.ydec
+                rw, rh = tl["width"] >> d.xdec, tl["height"] >> d.ydec
+                if (tl["x"] < 0).any() or (tl["y"] < 0).any() or \
+                        not _inside(ps[p], rx, ry, rx + rw, ry + rh):
+                    raise Rav1eHipError(f"{who}: a tile's region leaves a {name} plane")
+    prm = RvTxBlocksParams(int(bsize), int(tx_size), int(tx_type), int(luma_mode), int(chroma_mode),
+                           1 if skip else 0, 1 if luma_only else 0, 1 if need_recon_pixel else 0,
+                           1 if coeff_rate else 0, int(bit_depth))
+    for p in range(3):
+        prm.dc_delta_q[p], prm.ac_delta_q[p] = int(dc_delta_q[p]), int(ac_delta_q[p])
+    # sizes of the outputs: the layout, where the arguments have one
+    lay = RvTxBlocksLayout()
+    have = lib().rv_tx_blocks_layout(b, int(tx_size), xdec, ydec, 1 if luma_only else 0,
+                                     C.byref(lay)) == RV_OK
+    nb, nl = (lay.blocks_per_job, lay.levels_per_job) if have else (1, 1)
+    dt, dj = DeviceBuffer.from_array(tiles), DeviceBuffer.from_array(jobs)
+    dl, de, dd = DeviceBuffer(4 * nl * max(1, n)), DeviceBuffer(4 * nb * max(1, n)), \
+        DeviceBuffer(8 * nb * max(1, n))
+    sets = [_plane_set(ps, count) for ps in (rec, src, pred, dst)]
+    _check(lib().rv_tx_blocks_batch(sets[0], sets[1], sets[2], sets[3], dt.ptr, len(tiles), dj.ptr, n,
+                                    C.byref(prm), dl.ptr, de.ptr, dd.ptr, None), "rv_tx_blocks_batch")
+    _sync()
+    lv = dl.download(np.int32, nl * n).reshape(n, nl)
+    eo = de.download(np.uint32, nb * n).reshape(n, nb)
+    di = dd.download(np.uint64, nb * n).reshape(n, nb)
+    levels, eobs, dists = [], [], []
+    for p in range(lay.planes):
+        k, ca, f0, l0 = lay.n_blocks[p], lay.coded_area[p], lay.first_block[p], lay.level_off[p]
+        levels.append(lv[:, l0:l0 + k * ca].reshape(n, k, ca))
+        eobs.append(eo[:, f0:f0 + k])
+        dists.append(di[:, f0:f0 + k])
+    return lay, levels, eobs, dists
 
 
 # ---- chroma from luma (rv_cfl.hip) ------------------------------------------

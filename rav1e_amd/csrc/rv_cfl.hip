@@ -42,13 +42,6 @@ struct CflPlanes {
   rv_plane luma, rec_u, rec_v, src_u, src_v;
 };
 
-// get_scaled_luma_q0 (src/predict.rs:485-493)
-__device__ __forceinline__ int32_t cfl_scaled(int32_t alpha, int32_t ac) {
-  const int32_t q6 = alpha * ac;
-  const int32_t a0 = ((q6 < 0 ? -q6 : q6) + 32) >> 6;
-  return q6 < 0 ? -a0 : a0;
-}
-
 // Position of the run `k` of lane `gl`: pixel index, row, column.
 template <int G, int NP>
 __device__ __forceinline__ void cfl_run_pos(const CflGeom &g, int k, int gl, int &r, int &c) {

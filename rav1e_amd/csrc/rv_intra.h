@@ -313,15 +313,15 @@ __device__ __forceinline__ IntraEdgeGeo intra_edge_geo(int tx, int ty, int tw, i
 }
 
 // Entry i of edge_buf (src/partition.rs:559-690); entries no branch writes
-// are zero.  Each entry is computed from the plane alone, so any lane may
-// produce any entry.
-template <typename Px>
-__device__ __forceinline__ int32_t intra_edge_px(const rv_plane &p, const IntraEdgeGeo &g, int bd,
-                                                 int i) {
+// are zero.  Each entry is computed from the pixels alone, so any lane may
+// produce any entry.  D(r, c): the pixel at row r, column c of the tile's
+// region of the plane (the fused transform-block kernel reads the partition's
+// own pixels from its working copy, rv_tx_blocks.hip).
+template <typename Rd>
+__device__ __forceinline__ int32_t intra_edge_rd(const IntraEdgeGeo &g, int bd, int i, Rd D) {
   const int base = 128 << (bd - 8);
   const int L = 128, A = 129;
   const int x = g.x, y = g.y, w = g.w, h = g.h;
-  auto D = [&](int r, int c) -> int32_t { return (int32_t)*plane_ptr<Px>(p, g.tx + c, g.ty + r); };
   auto left = [&](int k) -> int32_t {  // left[2 * MAX_TX_SIZE - h + k]
     return x != 0 ? D(y + h - 1 - k, x - 1) : (y != 0 ? D(y - 1, 0) : base + 1);
   };
@@ -351,6 +351,22 @@ __device__ __forceinline__ int32_t intra_edge_px(const rv_plane &p, const IntraE
     return (g.needs & 1) ? left(0) : 0;  // left[2 * MAX_TX_SIZE - h] as the left branch left it
   }
   return 0;
+}
+
+// The same from a plane: pixel (0, 0) of the region is plane pixel (g.tx, g.ty).
+template <typename Px>
+__device__ __forceinline__ int32_t intra_edge_px(const rv_plane &p, const IntraEdgeGeo &g, int bd,
+                                                 int i) {
+  return intra_edge_rd(g, bd, i, [&](int r, int c) -> int32_t {
+    return (int32_t)*plane_ptr<Px>(p, g.tx + c, g.ty + r);
+  });
+}
+
+// get_scaled_luma_q0 (src/predict.rs:485-493)
+__device__ __forceinline__ int32_t cfl_scaled(int32_t alpha, int32_t ac) {
+  const int32_t q6 = alpha * ac;
+  const int32_t a0 = ((q6 < 0 ? -q6 : q6) + 32) >> 6;
+  return q6 < 0 ? -a0 : a0;
 }
 
 }  // namespace rv

@@ -10,30 +10,9 @@
 //
 // The fused form reads src - pred (diff, src/encoder.rs:1044-1058) straight
 // from the planes, so the i16 residual never exists in HBM.
-#include "rv_tx.h"
+#include "rv_tx2d.h"
 
 namespace rv {
-
-// FWD_SHIFT_* (forward.rs:22-40) by TxSize, shift_idx = (bd - 8) / 2.
-__constant__ int8_t kFwdShift[19][3][3] = {
-    {{3, 0, 0}, {2, 0, 1}, {0, 0, 3}},    {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},
-    {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},   {{4, -2, 0}, {2, 0, 0}, {0, 0, 2}},
-    {{4, -1, -2}, {2, 0, -1}, {0, 0, 1}}, {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},
-    {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},   {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},
-    {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},   {{4, -2, 0}, {2, 0, 0}, {0, 0, 2}},
-    {{4, -2, 0}, {2, 0, 0}, {0, 0, 2}},   {{4, -1, -2}, {2, 0, -1}, {0, 0, 1}},
-    {{4, -1, -2}, {2, 0, -1}, {0, 0, 1}}, {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},
-    {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},   {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},
-    {{4, -1, 0}, {2, 0, 1}, {0, 0, 3}},   {{4, -2, 0}, {2, 0, 0}, {0, 0, 2}},
-    {{4, -2, 0}, {2, 0, 0}, {0, 0, 2}}};
-
-// round_shift_array (src/transform/mod.rs:499-521): bit > 0 rounds right,
-// bit < 0 shifts left.
-__device__ __forceinline__ int32_t rsa(int32_t v, int bit) {
-  if (bit > 0) return round_shift(v, bit);
-  if (bit < 0) return (int32_t)((uint32_t)v << -bit);
-  return v;
-}
 
 enum FwdSrc { kFromResidual = 0, kFromPlanesU8 = 1, kFromPlanesU16 = 2 };
 
@@ -44,20 +23,6 @@ struct FwdArgs {
   int32_t *coeffs;
   int n, tx_size, ck, rk, shift_idx;
 };
-
-template <int KIND, int N>
-__device__ __forceinline__ void fwd_dispatch(int32_t *v) {
-  if constexpr (tx::fwd_supported(KIND, N)) tx::fwd1d<KIND, N>(v, v);
-}
-
-template <int N>
-__device__ __forceinline__ void fwd_kind(int kind, int32_t *v) {
-  switch (kind) {
-    case 0: fwd_dispatch<0, N>(v); break;
-    case 1: fwd_dispatch<1, N>(v); break;
-    default: fwd_dispatch<2, N>(v); break;  // Adst and FlipAdst (flip is 2-D)
-  }
-}
 
 template <int W, int H, int SRC>
 __global__ __launch_bounds__(64) void fwd_tx_kernel(FwdArgs a) {

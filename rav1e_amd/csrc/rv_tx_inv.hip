@@ -7,13 +7,9 @@
 // bits, column transforms, round_shift 4, add into the destination with a
 // clip to [0, 2^bd - 1].  Same wavefront layout as the forward launch:
 // 64 / max(W, H) blocks per wavefront, LDS rows padded to W + 1.
-#include "rv_tx.h"
+#include "rv_tx2d.h"
 
 namespace rv {
-
-// InvBlock::INTERMEDIATE_SHIFT (inverse.rs:1643-1666) by TxSize.
-__constant__ uint8_t kInvShift[19] = {0, 1, 2, 2, 2, 0, 0, 1, 1, 1,
-                                      1, 1, 1, 1, 1, 2, 2, 2, 2};
 
 struct InvArgs {
   const int32_t *coeffs;
@@ -21,19 +17,6 @@ struct InvArgs {
   const rv_tx_job *jobs;
   int n, tx_size, ck, rk, bd;
 };
-
-template <int KIND, int N>
-__device__ __forceinline__ void inv_dispatch(int32_t *v, int range) {
-  if constexpr (tx::inv_supported(KIND, N)) tx::inv1d<KIND, N>(v, range);
-}
-template <int N>
-__device__ __forceinline__ void inv_kind(int kind, int32_t *v, int range) {
-  switch (kind) {
-    case 0: inv_dispatch<0, N>(v, range); break;
-    case 1: inv_dispatch<1, N>(v, range); break;
-    default: inv_dispatch<2, N>(v, range); break;
-  }
-}
 
 template <int W, int H, typename Px>
 __global__ __launch_bounds__(64) void inv_tx_kernel(InvArgs a) {
