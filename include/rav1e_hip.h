@@ -1016,6 +1016,154 @@ int rv_ec_mode_fill_stacks(rv_ec_mode_job *d_jobs, int n, rv_mvref_geom geom,
                            const rv_mvref_tile *d_tiles, const rv_mv_blk *d_grid,
                            rv_mvref_result *d_stacks, uint32_t *d_status, void *stream);
 
+/* ---- the inter front of rdo_mode_decision (src/rdo.rs:784-1259) -----------
+ * What lies between the MV stacks / the searches and a candidate's transform
+ * blocks: the reference sets, the inter mode set with every candidate's MVs,
+ * and motion_compensate of the candidates.
+ *
+ * rv_inter_ref_sets_build, a pure host function, restates src/rdo.rs:815-835:
+ * allowed[n_allowed] are RefType codes (LAST_FRAME 1 .. ALTREF_FRAME 7) in
+ * InterConfig::allowed_ref_frames() order (src/api/internal.rs:190-199),
+ * ref_frames[7] is fi.ref_frames (RefType::to_index() -> DPB slot 0 .. 7).
+ * LAST3_FRAME is skipped (:818-820); a RefType whose slot an earlier set
+ * already has is skipped (:822); ref[i] / slot[i] describe single set i
+ * ([ref[i], NONE_FRAME], :829-831); fwd / bwd are the first set whose RefType
+ * is_fwd_ref (< 5) / is_bwd_ref (>= 5) (src/partition.rs:50-55), or -1
+ * (:823-828).  compound: the set {ref[fwd], ref[bwd]} follows the singles as
+ * set n_single, which needs both indices, reference_mode != SINGLE and
+ * min(bsize.width_mi(), bsize.height_mi()) >= 2 (:914-927).  RV_EINVAL for a
+ * null pointer, n_allowed outside 1..7, a RefType outside 1..7, a slot
+ * outside 0..7, a value that is no BlockSize, or no set at all (the
+ * reference's assert, :834). */
+#define RV_INTER_MAX_SETS 8   /* 7 single sets and the compound one */
+#define RV_INTER_MAX_CANDS 20 /* the ArrayVec's capacity (src/rdo.rs:837) */
+typedef struct rv_inter_ref_sets {
+  int32_t n_single;
+  int32_t ref[7];
+  int32_t slot[7];
+  int32_t fwd, bwd;
+  int32_t compound;
+} rv_inter_ref_sets;
+int rv_inter_ref_sets_build(const int32_t *allowed, int n_allowed, const int32_t *ref_frames,
+                            int reference_mode_not_single, int bsize, rv_inter_ref_sets *out);
+
+/* rv_inter_mode_set_batch: src/rdo.rs:858-986 for n blocks that share their
+ * reference sets, one launch.  n_sets = sets.n_single + sets.compound.
+ * d_stacks[n][n_sets]: what rv_find_mvrefs_batch wrote for the queries of
+ * each set, entry n_single being the compound query (:928-936).
+ * d_me[n][n_single]: motion_estimation's result per single set (:869-878).
+ * d_lists[n]: the candidates in the reference's push order.  Per single set i
+ * (:880-909): NEARESTMV (RAV1E_INTER_MODES_MINIMAL); NEAR0MV if the stack is
+ * not empty; GLOBALMV if its length is >= 2; under include_near_mvs NEAR1MV at
+ * length >= 3 and NEAR2MV at >= 4; NEWMV if me[i] is not zero and none of the
+ * first 2 (4 under include_near_mvs) stack entries has it as this_mv.  Then
+ * the six RAV1E_INTER_COMPOUND_MODES (src/predict.rs:51-58) on the compound
+ * set (:937-939).  A record holds the mode, its set, the set's RefTypes
+ * ([ref, NONE_FRAME] or [ref[fwd], ref[bwd]]), mode_contexts[set] and the MVs
+ * of :950-986: NEWMV / NEW_NEWMV mvs_from_me[set] ([me[i], 0], the compound
+ * set's [me[fwd], me[bwd]], :925-927); NEARESTMV / NEAREST_NEARESTMV entry 0's
+ * {this_mv, comp_mv} or zero on an empty stack; NEAR0MV / NEAR_NEARMV entry 1's
+ * or zero at length <= 1; NEAR1MV / NEAR2MV entry luma_mode - NEAR0MV + 1;
+ * NEAREST_NEWMV {entry 0's this_mv, mvs_from_me[1]}; NEW_NEARESTMV
+ * {mvs_from_me[0], entry 0's comp_mv}; the GLOBAL modes zero.
+ *
+ * Two inputs make the reference panic instead of deciding: a list longer than
+ * RV_INTER_MAX_CANDS (the ArrayVec's capacity, :837; three single sets with
+ * near MVs and the compound modes reach 24), and mv_stacks[i][0] of an empty
+ * compound stack (:974-979).  A block that meets either is rejected: counted
+ * in d_status (cleared here), its list gets count 0 and it gets no MC jobs.
+ * A stack length outside 0..9 rejects the block as well.
+ *
+ * d_mc_jobs (may be NULL, then d_blocks may be too): [n][RV_INTER_MAX_CANDS]
+ * jobs for rv_motion_compensate_batch, candidate k of block b at [b][k] with
+ * the block's tile and offset from d_blocks[b], dst_set = k, ref_slot =
+ * sets.slot of the candidate's references; unused entries get tile = -1.
+ * RV_EINVAL, before any launch: null pointers, n < 0, a sets value
+ * rv_inter_ref_sets_build could not have produced. */
+typedef struct rv_inter_cand {
+  int32_t luma_mode; /* PredictionMode, 14 NEARESTMV .. 27 NEW_NEWMV */
+  int32_t set;
+  int32_t ref[2];    /* RefType; ref[1] = 8 (NONE_FRAME) on a single set */
+  rv_mv mv[2];
+  int32_t mode_context;
+} rv_inter_cand;
+typedef struct rv_inter_list {
+  int32_t n;
+  rv_inter_cand cand[RV_INTER_MAX_CANDS];
+} rv_inter_list;
+typedef struct rv_inter_blk {
+  int32_t tile, bo_x, bo_y; /* tile-relative 4x4 luma units */
+} rv_inter_blk;
+typedef struct rv_inter_mc_job {
+  int32_t tile;        /* < 0: the entry is skipped */
+  int32_t bo_x, bo_y;  /* tile_bo, tile-relative 4x4 luma units */
+  int32_t dst_set;
+  int32_t ref_slot[2]; /* ref_slot[1] < 0: single reference */
+  rv_mv mv[2];
+} rv_inter_mc_job;
+int rv_inter_mode_set_batch(const rv_mvref_result *d_stacks, const rv_mv *d_me,
+                            const rv_inter_blk *d_blocks, int n, rv_inter_ref_sets sets,
+                            int include_near_mvs, rv_inter_list *d_lists,
+                            rv_inter_mc_job *d_mc_jobs, uint32_t *d_status, void *stream);
+
+/* rv_motion_compensate_batch: motion_compensate (src/encoder.rs:1239-1430,
+ * the arm of :1416-1428) through predict_inter (src/predict.rs:255-338) for n
+ * jobs of one bsize and every coded plane, in one launch.  refs: n_refs sets of
+ * 3 planes (set s, plane p at refs[3 * s + p]), the table a job's ref_slot
+ * indexes; dsts: n_dsts sets of 3 planes a job's dst_set indexes, so several
+ * candidates at one position go to different sets.  With luma_only (:1251-1256)
+ * only plane 0 of a set is read.  Per plane:
+ *  - the block is bsize (luma) or bsize.subsampled_size(xdec, ydec) (:1260-1261);
+ *    po = tile_bo.plane_offset (:1264), frame_po = tile_rect.decimated(xdec,
+ *    ydec).to_frame_plane_offset(po) (:1266, predict.rs:261);
+ *  - get_params (predict.rs:267-284): shift = 3 + ydec / 3 + xdec, offset =
+ *    mv >> shift (arithmetic), frac = (mv - (offset << shift)) << (4 - shift),
+ *    the window's origin frame_po + offset - 3 clamped by PlaneSlice::clamp
+ *    (src/frame/plane.rs:521-533: x into [-xorigin, width], y into [-yorigin,
+ *    height]), then + 3;
+ *  - a single reference: put_8tap; compound (ref_slot[1] >= 0): prep_8tap of
+ *    both references and mc_avg (predict.rs:286-337), the i16 intermediates
+ *    never leaving the chip; filter_mode (fi.default_filter, :263) serves both
+ *    directions, the tap set per direction by the block's length (get_filter,
+ *    src/mc.rs:201-210: a 4-long side takes the 4-tap sets); intermediate_bits
+ *    is 2 at 12 bit, else 4 (src/mc.rs:222, 318, 394);
+ *  - the result goes to the destination set at frame_po.
+ * bsize: 8x8 .. 64x64 and the 2:1 / 1:2 sizes; 4:4:4, 4:2:2, 4:2:0 (the chroma
+ * planes' xdec / ydec); 8 / 10 / 12 bit.
+ * RV_ENOTSUP, before any launch: 4xN / Nx4 (the chroma arm of :1269-1415 reads
+ * the neighbours' MVs), the 4:1 / 1:4 sizes and sizes above 64x64, a (bsize,
+ * layout) without a subsampled_size (8x16, 16x32, 32x64 at 4:2:2).
+ * RV_EINVAL, before any launch: a value that is no BlockSize or FilterMode; a
+ * bit depth other than 8 / 10 / 12 or one the planes' pixel type does not
+ * hold; a subsampling other than the three layouts; plane sets that differ in
+ * subsampling or geometry (stride, allocation, origin, size); a destination
+ * set that overlaps a reference set or another destination set; null pointers;
+ * n < 0; n_refs outside 1..8; n_dsts outside 1..RV_INTER_MAX_CANDS; a
+ * reference plane whose allocation does not hold the furthest clamped window
+ * of this bsize (column width + w + 6 and row height + h + 6 of the plane).
+ * Every MV is legal: the clamp keeps any i16 MV's window inside the padding.
+ * Jobs are device data and checked there: a job whose tile, ref_slot or
+ * dst_set is out of range, whose offset is negative, not a multiple of the
+ * block's size or leaves its tile, or whose block leaves a destination plane's
+ * allocation is rejected: counted in d_status (cleared here), it reads no
+ * pixel and writes nothing.  A job with tile < 0 is skipped and not counted. */
+typedef struct rv_inter_mc_params {
+  int32_t bsize, filter_mode, luma_only, bit_depth;
+} rv_inter_mc_params;
+int rv_motion_compensate_batch(const rv_plane *refs, int n_refs, const rv_plane *dsts, int n_dsts,
+                               const rv_intra_tile *d_tiles, int n_tiles,
+                               const rv_inter_mc_job *d_jobs, int n,
+                               const rv_inter_mc_params *params, uint32_t *d_status, void *stream);
+/* The same launch with the lanes that share a job stated (a power of two,
+ * 16 .. 256; 0: the default for the size), for measuring the packing.
+ * RV_EINVAL for another value, or one so small that the 256 / lanes jobs of a
+ * workgroup need more than 64 KiB of LDS at this bsize. */
+int rv_motion_compensate_batch_lanes(const rv_plane *refs, int n_refs, const rv_plane *dsts,
+                                     int n_dsts, const rv_intra_tile *d_tiles, int n_tiles,
+                                     const rv_inter_mc_job *d_jobs, int n,
+                                     const rv_inter_mc_params *params, uint32_t *d_status,
+                                     int lanes, void *stream);
+
 /* The importance propagation of compute_block_importances
  * (src/api/internal.rs:823-1010) for one (frame, reference) pass, bit-exact
  * in f32.  org: the frame's luma plane; ref: the reference's; d_mvs,

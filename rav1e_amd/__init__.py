@@ -224,6 +224,21 @@ class RvMvrefGeom(C.Structure):
                                          "frame_rows")] + [("sign_bias", C.c_uint32)]
 
 
+class RvInterRefSets(C.Structure):
+    """rv_inter_ref_sets (include/rav1e_hip.h)."""
+    _fields_ = [("n_single", C.c_int32), ("ref", C.c_int32 * 7), ("slot", C.c_int32 * 7),
+                ("fwd", C.c_int32), ("bwd", C.c_int32), ("compound", C.c_int32)]
+
+    @property
+    def n_sets(self):
+        return self.n_single + self.compound
+
+
+class RvInterMcParams(C.Structure):
+    """rv_inter_mc_params (include/rav1e_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("bsize", "filter_mode", "luma_only", "bit_depth")]
+
+
 def _declare(L):
     vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
     P = C.POINTER(RvPlane)
@@ -378,6 +393,11 @@ def _declare(L):
         "rv_mvref_grid_paint": (i32, [vp, i32, RvMvrefGeom, vp, vp, vp, vp, vp]),
         "rv_find_mvrefs_batch": (i32, [vp, i32, RvMvrefGeom, vp, vp, vp, vp, vp]),
         "rv_ec_mode_fill_stacks": (i32, [vp, i32, RvMvrefGeom, vp, vp, vp, vp, vp]),
+        "rv_inter_ref_sets_build": (i32, [vp, i32, vp, i32, i32, vp]),
+        "rv_inter_mode_set_batch": (i32, [vp, vp, vp, i32, RvInterRefSets, i32, vp, vp, vp, vp]),
+        "rv_motion_compensate_batch": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp]),
+        "rv_motion_compensate_batch_lanes": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32,
+                                                   vp]),
         "rv_sad_fn": (vp, [i32, i32, i32]),
         "rv_satd_fn": (vp, [i32, i32, i32]),
         "rv_put_fn_get": (vp, [i32, i32, i32]),
@@ -2453,6 +2473,125 @@ def ec_fill_mode_stacks(jobs, grid, check=True, info=None):
         raise Rav1eHipError(f"ec_fill_mode_stacks: {rejected} inter jobs outside the supported "
                             "sizes, their tile or the reference codes")
     return filled, full["stack"]["this_mv"][:, :4].astype(np.int32)
+
+
+# ---- the inter front of rdo_mode_decision (rv_inter.hip) ----------------------
+# rv_inter_cand, rv_inter_list, rv_inter_blk, rv_inter_mc_job; an MV is (row, col)
+INTER_MAX_CANDS = 20  # RV_INTER_MAX_CANDS
+INTER_CAND = np.dtype([("luma_mode", "<i4"), ("set", "<i4"), ("ref", "<i4", 2),
+                       ("mv", "<i2", (2, 2)), ("mode_context", "<i4")])
+INTER_LIST = np.dtype([("n", "<i4"), ("cand", INTER_CAND, INTER_MAX_CANDS)])
+INTER_BLK = np.dtype([("tile", "<i4"), ("bo_x", "<i4"), ("bo_y", "<i4")])
+INTER_MC_JOB = np.dtype([("tile", "<i4"), ("bo_x", "<i4"), ("bo_y", "<i4"), ("dst_set", "<i4"),
+                         ("ref_slot", "<i4", 2), ("mv", "<i2", (2, 2))])
+
+
+def _check_code(rc, what):
+    if rc != RV_OK:
+        err = Rav1eHipError(f"{what} failed ({rc}): {lib().rv_last_error().decode()}")
+        err.code = rc
+        raise err
+
+
+def inter_ref_sets(allowed, ref_frames, compound_allowed, bsize) -> RvInterRefSets:
+    """rv_inter_ref_sets_build (src/rdo.rs:815-835, 914-927): the single
+    reference sets of rdo_mode_decision -- allowed: RefType codes 1..7 in
+    InterConfig::allowed_ref_frames() order, ref_frames: fi.ref_frames, the
+    seven RefTypes' DPB slots -- with LAST3_FRAME skipped and one set per
+    distinct slot, the first forward / backward set, and whether the compound
+    set follows (compound_allowed: reference_mode != SINGLE).  Raises with
+    the library's code (Rav1eHipError.code) on bad arguments."""
+    al = np.ascontiguousarray(allowed, np.int32).reshape(-1)
+    rf = np.ascontiguousarray(ref_frames, np.int32).reshape(-1)
+    if len(rf) != 7:
+        raise Rav1eHipError("inter_ref_sets: ref_frames has seven slots")
+    out = RvInterRefSets()
+    _check_code(lib().rv_inter_ref_sets_build(al.ctypes.data, len(al), rf.ctypes.data,
+                                              1 if compound_allowed else 0, int(bsize),
+                                              C.byref(out)), "rv_inter_ref_sets_build")
+    return out
+
+
+def inter_mode_set_batch(stacks, me, sets: RvInterRefSets, include_near_mvs=False, blocks=None):
+    """rv_inter_mode_set_batch: the inter mode set of src/rdo.rs:858-986 with
+    every candidate's MVs for n blocks in one launch.  stacks: MVREF_RESULT
+    (n, sets.n_sets) as find_mvrefs_batch wrote them per reference set (the
+    compound query last); me: (n, sets.n_single, 2) int16 (row, col), the
+    searches' MVs; blocks: INTER_BLK [n] when the MC jobs are wanted.  Returns
+    (lists INTER_LIST [n], mc_jobs INTER_MC_JOB (n, 20) or None, rejected):
+    rejected blocks (a list above 20 entries, an empty compound stack: the
+    reference panics on both) have n = 0 and no jobs."""
+    who = "inter_mode_set_batch"
+    st = np.ascontiguousarray(stacks, MVREF_RESULT)
+    ns, nsets = sets.n_single, sets.n_sets
+    st = st.reshape(-1, nsets) if st.size else st.reshape(0, nsets)
+    n = len(st)
+    mv = np.ascontiguousarray(me, np.int16)
+    if mv.size != n * ns * 2:
+        raise Rav1eHipError(f"{who}: me is (n, {ns}, 2) for {n} blocks")
+    lists = np.zeros(n, INTER_LIST)
+    blk = None
+    if blocks is not None:
+        blk = np.ascontiguousarray(blocks, INTER_BLK).reshape(-1)
+        if len(blk) != n:
+            raise Rav1eHipError(f"{who}: one INTER_BLK per block")
+    if n == 0:
+        return lists, (np.zeros((0, INTER_MAX_CANDS), INTER_MC_JOB) if blk is not None else None), 0
+    ds, dm, dl, dst = DeviceBuffer.from_array(st), DeviceBuffer.from_array(mv), \
+        DeviceBuffer(lists.nbytes), DeviceBuffer(4)
+    db = DeviceBuffer.from_array(blk) if blk is not None else None
+    dj = DeviceBuffer(n * INTER_MAX_CANDS * INTER_MC_JOB.itemsize) if blk is not None else None
+    _check_code(lib().rv_inter_mode_set_batch(ds.ptr, dm.ptr, db.ptr if db else None, n, sets,
+                                              1 if include_near_mvs else 0, dl.ptr,
+                                              dj.ptr if dj else None, dst.ptr, None),
+                "rv_inter_mode_set_batch")
+    _sync(None)
+    lists = dl.download(INTER_LIST, n)
+    jobs = dj.download(INTER_MC_JOB, n * INTER_MAX_CANDS).reshape(n, INTER_MAX_CANDS) if dj else None
+    return lists, jobs, int(dst.download(np.uint32)[0])
+
+
+def _plane_sets(who, sets, count):
+    """Sequences of plane sets (3 DevicePlanes each, `count` of them used) as
+    the library's [n][3] rv_plane table."""
+    sets = list(sets)
+    arr = (RvPlane * (3 * max(1, len(sets))))()
+    for s, ps in enumerate(sets):
+        if len(ps) < count:
+            raise Rav1eHipError(f"{who}: a plane set needs {count} plane(s)")
+        for p in range(count):
+            arr[3 * s + p] = ps[p].desc
+    return arr, len(sets)
+
+
+def motion_compensate_batch(refs, dsts, tiles, jobs, bsize, filter_mode=FilterMode.REGULAR,
+                            luma_only=False, bit_depth=8, lanes=0):
+    """rv_motion_compensate_batch: motion_compensate (src/encoder.rs:1239-1430)
+    through predict_inter (src/predict.rs:255-338) for n jobs of one bsize and
+    every coded plane in one launch.  refs: the reference plane sets a job's
+    ref_slot indexes, dsts: the destination sets its dst_set indexes (each set
+    three DevicePlanes, one with luma_only); tiles INTRA_TILE; jobs
+    INTER_MC_JOB (tile, tile_bo in 4x4 luma units, dst_set, ref_slot --
+    ref_slot[1] < 0: single reference -- and the MVs as (row, col)).  Jobs with
+    tile < 0 are skipped.  lanes: the lanes that share a job (0: the default
+    of the size).  Returns the number of rejected jobs (an index out of range,
+    a block not aligned to its size or outside its tile); they write nothing."""
+    who = "motion_compensate_batch"
+    tiles = np.ascontiguousarray(tiles, dtype=INTRA_TILE).reshape(-1)
+    jobs = np.ascontiguousarray(jobs, dtype=INTER_MC_JOB).reshape(-1)
+    count = 1 if luma_only else 3
+    ra, nr = _plane_sets(who, refs, count)
+    da, nd = _plane_sets(who, dsts, count)
+    if nr == 0 or nd == 0:
+        raise Rav1eHipError(f"{who}: at least one reference set and one destination set")
+    prm = RvInterMcParams(int(bsize), int(filter_mode), 1 if luma_only else 0, int(bit_depth))
+    n = len(jobs)
+    dt, dj, dst = DeviceBuffer.from_array(tiles), DeviceBuffer.from_array(jobs), DeviceBuffer(4)
+    _check_code(lib().rv_motion_compensate_batch_lanes(ra, nr, da, nd, dt.ptr, len(tiles), dj.ptr,
+                                                       n, C.byref(prm), dst.ptr, int(lanes), None),
+                "rv_motion_compensate_batch")
+    _sync(None)
+    return int(dst.download(np.uint32)[0])
 
 
 def prep_8tap_batch(src: DevicePlane, jobs, w, h, mode_x=0, mode_y=0, bit_depth=8):
