@@ -1164,6 +1164,175 @@ int rv_motion_compensate_batch_lanes(const rv_plane *refs, int n_refs, const rv_
                                      const rv_inter_mc_params *params, uint32_t *d_status,
                                      int lanes, void *stream);
 
+/* ---- a block's mode decision: distortion, RD cost and the winner ----------
+ * The end of rdo_mode_decision (src/rdo.rs:784-1259) over candidates whose
+ * pixels (rv_motion_compensate_batch, rv_tx_blocks_batch), transform
+ * distortions and eobs (rv_tx_blocks_batch) and rates (rv_ec_cand_rates) are
+ * already in device memory: each candidate's ScaledDistortion as
+ * luma_chroma_mode_rdo takes it (:736-751), compute_rd_cost (:563-568), the
+ * walk over the candidates in the reference's order with its early-outs, and
+ * the PartitionParameters of the winner.
+ *
+ * rv_segmentation_data: segmentation_optimize's three ALT_Q deltas (src/
+ * segmentation.rs:29-48): 0, 21 and max(-21, 1 - base_q_idx).  Host only.
+ * RV_EINVAL: base_q_idx outside 0 .. 255, a null pointer.
+ *
+ * rv_block_segment_batch, one lane per block of one bsize (rv_mode_block;
+ * cand_first / cand_count are not read):
+ *  - compute_mean_importance (src/rdo.rs:477-493) of the block at
+ *    ts.to_frame_block_offset(tile_bo) = tile / 4 + bo: f32 sums in y-then-x
+ *    order over the 4x4 blocks inside w_in_b x h_in_b, divided by the full
+ *    area; d_importance [..][w_imp] is block_importances, NULL: all zero;
+ *  - the heuristic sidx of luma_chroma_mode_rdo with quantizer_rdo off
+ *    (:655-679): importance [0, 2) -> 1, [2, 4) -> 0, >= 4 -> 2, and 0 when
+ *    base_q_idx + data[sidx] < 2;
+ *  - get_qidx (src/encoder.rs:1061-1072): clamp(base_q_idx + data[sidx], 0,
+ *    255), what rv_tx_blocks_job.qindex takes.
+ * d_sidx, d_qindex, d_mean: [n].  bsize: any BlockSize up to 64x64 that is no
+ * 4:1 / 1:4 size (RV_ENOTSUP above; RV_EINVAL for no BlockSize).  A block with
+ * a tile out of range or a negative offset is counted in d_status[0] (cleared
+ * here), reads nothing and yields sidx 0, qindex base_q_idx, mean 0.
+ *
+ * rv_mode_decide_batch, n blocks of one bsize in one launch.  The block sizes,
+ * layouts, bit depths and their RV_ENOTSUP / RV_EINVAL codes are those of
+ * rv_tx_blocks_batch.  src: 3 planes; cands: n_sets sets of 3 planes (set s,
+ * plane p at cands[3 * s + p], as rv_motion_compensate_batch's dsts) a
+ * candidate's `set` indexes; commit (may be NULL): 3 planes.  Every plane p of
+ * src, of every set and of commit has one geometry.  A block's candidates are
+ * d_cands[cand_first .. cand_first + cand_count), in the reference's order of
+ * evaluation.  A candidate:
+ *  - group: the index of its luma_chroma_mode_rdo call; a group's candidates
+ *    are contiguous;
+ *  - flags: RV_MODE_CAND_SKIP, _INTRA (luma_mode_is_intra), _NEED_RECON_PIXEL;
+ *  - rate: wr.tell_frac() - tell in 1/8 bit (rv_ec_cand_rates);
+ *  - tx_size, dist_off, eob_off: its row of rv_tx_blocks_batch's d_dist / d_eob
+ *    (blocks_per_job entries as rv_tx_blocks_layout(bsize, tx_size) lays them
+ *    out) starts at d_dist + dist_off / d_eob + eob_off, arrays of n_tx
+ *    entries; not read for a skip candidate;
+ *  - pay: copied to the winner untouched.
+ * Distortion (u64, every f64 step the reference's, in its order):
+ *  - pixel path, when !use_tx_domain_distortion or need_recon_pixel:
+ *    compute_distortion (:338-411).  Luma: cdef_dist_wxh under
+ *    RV_TUNE_PSYCHOVISUAL, else sse_wxh, per 8x8 importance sub-block
+ *    `(value as f64 * bias) as u64` with the bias of BLOCK_8X8 at the
+ *    sub-block, summed, then `* dist_scale[0]` truncated.  Chroma: sse_wxh over
+ *    w_uv x h_uv with its sub-blocks of min(8, w_uv) >> xdec by min(8, h_uv) >>
+ *    ydec pixels, each biased as the min(8, w_uv) x min(8, h_uv) BlockSize at
+ *    its own offset (an 8x8 block at 4:2:0: four 2x2 sub-blocks biased as
+ *    BLOCK_4X4), each plane `* dist_scale[p]` truncated before the add;
+ *  - tx path (compute_tx_distortion, :414-475): a skip candidate takes the
+ *    biased sse_wxh of the three planes as above; another the sum over its
+ *    transform blocks of `RawDistortion(d) * bias * dist_scale[p]` (src/
+ *    encoder.rs:1234-1236), the bias that of the partition's bsize at the
+ *    transform block's tx_bo (chroma: :1864-1869).
+ * cost = distortion as f64 + lambda * (rate as f64 / 8.0).  has_coeff: false
+ * for a skip candidate (src/encoder.rs:1140-1142, 1914-1916); else the OR over
+ * the transform blocks of eob != 0 when need_recon_pixel || coeff_rate, and
+ * true otherwise (:1173-1189, 1812).
+ * The walk: best starts at d_seed[b] (may be NULL: rd_cost f64::MAX, skip
+ * false) and is replaced on `rd < best.rd_cost` only.  Of an inter group the
+ * skip candidates come first; if the last of them that replaced best had
+ * distortion 0, the group's other candidates are gated out (:774-780).  An
+ * intra group is gated out when best.skip holds as its first candidate is
+ * reached (:1008).  A gated candidate's distortion and cost are still written.
+ * The CfL trial (:1155-1236) is a second launch seeded with the first one's
+ * decision.
+ * Outputs: d_out[n]; per candidate d_cand_dist, d_cand_cost, d_cand_state
+ * (RV_MODE_STATE_*; all three cleared here).  With commit, the winner's
+ * partition pixels of the three planes are copied from its set; nothing is
+ * written when no candidate of this launch won (cand = -1).
+ * RV_EINVAL, before any launch: what rv_tx_blocks_batch refuses; a tune that
+ * is no RV_TUNE_*; use_tx_domain_distortion under RV_TUNE_PSYCHOVISUAL
+ * (compute_tx_distortion's assert, :419); n_sets outside 1 ..
+ * RV_INTER_MAX_CANDS; planes that differ in geometry or subsampling; commit
+ * overlapping a candidate set; w_in_b / h_in_b < 1, an importance plane with
+ * w_imp < ceil(w_in_b / 2); negative counts; null pointers.
+ * Blocks and candidates are device data and checked there.  A block with a
+ * tile out of range, an offset that is negative, not a multiple of the block's
+ * size or outside its tile or the planes' allocations, or a candidate range
+ * outside d_cands is counted in d_status[0]: it reads no pixel, yields cand =
+ * -1 with the default decision and commits nothing.  A candidate with a set
+ * out of range, a tx_size that is none or larger than bsize, or (not skip) a
+ * row that leaves d_dist / d_eob is counted in d_status[1]: it reads nothing,
+ * gets RV_MODE_STATE_REJECTED and the walk passes over it.  d_status: two
+ * words, cleared here. */
+#define RV_TUNE_PSNR 0
+#define RV_TUNE_PSYCHOVISUAL 1
+#define RV_MODE_CAND_SKIP 1
+#define RV_MODE_CAND_INTRA 2
+#define RV_MODE_CAND_NEED_RECON_PIXEL 4
+#define RV_MODE_STATE_NONE 0          /* not visited: its block was rejected */
+#define RV_MODE_STATE_EVALUATED 1
+#define RV_MODE_STATE_GATED_ZERO_DIST 2 /* its group's skip pass had distortion 0 */
+#define RV_MODE_STATE_GATED_SKIP 3      /* an intra group reached with best.skip */
+#define RV_MODE_STATE_REJECTED 4
+typedef struct rv_mode_payload {
+  int32_t luma_mode, chroma_mode; /* PredictionMode */
+  int32_t ref_frames[2];
+  rv_mv mvs[2];
+  int32_t tx_type, sidx;
+  int32_t alpha_u, alpha_v;       /* pred_cfl_params */
+} rv_mode_payload;
+typedef struct rv_mode_cand {
+  int32_t group, flags, set;
+  uint32_t rate;
+  int32_t tx_size;
+  int32_t dist_off, eob_off;
+  rv_mode_payload pay;
+} rv_mode_cand;
+typedef struct rv_mode_block {
+  int32_t tile;
+  int32_t bo_x, bo_y; /* tile-relative 4x4 luma units */
+  int32_t cand_first, cand_count;
+} rv_mode_block;
+typedef struct rv_mode_decision {
+  double rd_cost;
+  uint64_t distortion;
+  uint32_t rate;
+  int32_t cand;       /* index into d_cands of this launch's winner, or -1 */
+  int32_t skip, has_coeff;
+  int32_t tx_size, reserved;
+  rv_mode_payload pay;
+} rv_mode_decision;
+typedef struct rv_mode_decide_params {
+  int32_t bsize, bit_depth;
+  int32_t tune, use_tx_domain_distortion, coeff_rate;
+  int32_t w_in_b, h_in_b, w_imp; /* fi.w_in_b, fi.h_in_b, fi.w_in_imp_b */
+  double lambda;
+  double dist_scale[3];
+} rv_mode_decide_params;
+int rv_segmentation_data(int base_q_idx, int16_t data[3]);
+int rv_block_segment_batch(const rv_intra_tile *d_tiles, int n_tiles, const rv_mode_block *d_blocks,
+                           int n, int bsize, int base_q_idx, const int16_t data[3],
+                           const float *d_importance, int w_imp, int w_in_b, int h_in_b,
+                           int32_t *d_sidx, int32_t *d_qindex, float *d_mean, uint32_t *d_status,
+                           void *stream);
+int rv_mode_decide_batch(const rv_plane *src, const rv_plane *cands, int n_sets,
+                         const rv_plane *commit, const rv_intra_tile *d_tiles, int n_tiles,
+                         const rv_mode_block *d_blocks, int n, const rv_mode_cand *d_cands,
+                         int n_cands, const rv_mode_decision *d_seed, const uint64_t *d_dist,
+                         const uint32_t *d_eob, int n_tx, const float *d_importance,
+                         const rv_mode_decide_params *params, rv_mode_decision *d_out,
+                         uint64_t *d_cand_dist, double *d_cand_cost, int32_t *d_cand_state,
+                         uint32_t *d_status, void *stream);
+/* Pure host function: the launch's argument checks that need no device data
+ * (everything above that is refused "before any launch"), with its codes. */
+int rv_mode_decide_check(const rv_plane *src, const rv_plane *cands, int n_sets,
+                         const rv_plane *commit, const rv_mode_decide_params *params,
+                         int has_importance, int lanes);
+/* The same launch with the lanes that share a block stated (a power of two,
+ * 8 .. 256; 0: the default for the size), for measuring the packing.
+ * RV_EINVAL for another value, or one so small that the 256 / lanes blocks of a
+ * workgroup need more than 64 KiB of LDS at this bsize. */
+int rv_mode_decide_batch_lanes(const rv_plane *src, const rv_plane *cands, int n_sets,
+                               const rv_plane *commit, const rv_intra_tile *d_tiles, int n_tiles,
+                               const rv_mode_block *d_blocks, int n, const rv_mode_cand *d_cands,
+                               int n_cands, const rv_mode_decision *d_seed, const uint64_t *d_dist,
+                               const uint32_t *d_eob, int n_tx, const float *d_importance,
+                               const rv_mode_decide_params *params, rv_mode_decision *d_out,
+                               uint64_t *d_cand_dist, double *d_cand_cost, int32_t *d_cand_state,
+                               uint32_t *d_status, int lanes, void *stream);
+
 /* The importance propagation of compute_block_importances
  * (src/api/internal.rs:823-1010) for one (frame, reference) pass, bit-exact
  * in f32.  org: the frame's luma plane; ref: the reference's; d_mvs,

@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import enum
 import os
+import typing
 
 import numpy as np
 
@@ -398,6 +399,14 @@ def _declare(L):
         "rv_motion_compensate_batch": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp]),
         "rv_motion_compensate_batch_lanes": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32,
                                                    vp]),
+        "rv_segmentation_data": (i32, [i32, vp]),
+        "rv_block_segment_batch": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp,
+                                         vp, vp]),
+        "rv_mode_decide_check": (i32, [vp, vp, i32, vp, vp, i32, i32]),
+        "rv_mode_decide_batch": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp,
+                                       vp, vp, vp, vp, vp, vp, vp]),
+        "rv_mode_decide_batch_lanes": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32,
+                                             vp, vp, vp, vp, vp, vp, vp, i32, vp]),
         "rv_sad_fn": (vp, [i32, i32, i32]),
         "rv_satd_fn": (vp, [i32, i32, i32]),
         "rv_put_fn_get": (vp, [i32, i32, i32]),
@@ -2592,6 +2601,198 @@ def motion_compensate_batch(refs, dsts, tiles, jobs, bsize, filter_mode=FilterMo
                 "rv_motion_compensate_batch")
     _sync(None)
     return int(dst.download(np.uint32)[0])
+
+
+# ---- a block's mode decision (rv_mode_decide.hip) ---------------------------
+class Tune(enum.IntEnum):
+    """Tune (src/api/config/encoder.rs): RV_TUNE_*."""
+    Psnr = 0
+    Psychovisual = 1
+
+
+MODE_CAND_SKIP, MODE_CAND_INTRA, MODE_CAND_NEED_RECON_PIXEL = 1, 2, 4  # RV_MODE_CAND_*
+(MODE_STATE_NONE, MODE_STATE_EVALUATED, MODE_STATE_GATED_ZERO_DIST, MODE_STATE_GATED_SKIP,
+ MODE_STATE_REJECTED) = range(5)  # RV_MODE_STATE_*
+MODE_PAYLOAD = np.dtype([("luma_mode", "<i4"), ("chroma_mode", "<i4"), ("ref_frames", "<i4", 2),
+                         ("mvs", "<i2", (2, 2)), ("tx_type", "<i4"), ("sidx", "<i4"),
+                         ("alpha_u", "<i4"), ("alpha_v", "<i4")])
+MODE_CAND = np.dtype([("group", "<i4"), ("flags", "<i4"), ("set", "<i4"), ("rate", "<u4"),
+                      ("tx_size", "<i4"), ("dist_off", "<i4"), ("eob_off", "<i4"),
+                      ("pay", MODE_PAYLOAD)])
+MODE_BLOCK = np.dtype([("tile", "<i4"), ("bo_x", "<i4"), ("bo_y", "<i4"), ("cand_first", "<i4"),
+                       ("cand_count", "<i4")])
+MODE_DECISION = np.dtype([("rd_cost", "<f8"), ("distortion", "<u8"), ("rate", "<u4"),
+                          ("cand", "<i4"), ("skip", "<i4"), ("has_coeff", "<i4"),
+                          ("tx_size", "<i4"), ("reserved", "<i4"), ("pay", MODE_PAYLOAD)])
+RD_COST_MAX = float(np.finfo(np.float64).max)  # f64::MAX, PartitionParameters::default()
+
+
+class RvModeDecideParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("bsize", "bit_depth", "tune", "use_tx_domain_distortion",
+                                         "coeff_rate", "w_in_b", "h_in_b", "w_imp")] + \
+               [("lambda_", C.c_double), ("dist_scale", C.c_double * 3)]
+
+
+class ModeDecision(typing.NamedTuple):
+    """PartitionParameters as rdo_mode_decision returns them (src/rdo.rs:
+    1244-1258), from one MODE_DECISION record: `cand` is the winner's index in
+    the launch's candidate list, -1 when none of them won."""
+    cand: int
+    rd_cost: float
+    distortion: int
+    rate: int
+    skip: bool
+    has_coeff: bool
+    pred_mode_luma: int
+    pred_mode_chroma: int
+    ref_frames: tuple
+    mvs: tuple
+    tx_size: int
+    tx_type: int
+    sidx: int
+    pred_cfl_params: tuple
+
+    @classmethod
+    def from_record(cls, r):
+        p = r["pay"]
+        return cls(int(r["cand"]), float(r["rd_cost"]), int(r["distortion"]), int(r["rate"]),
+                   bool(r["skip"]), bool(r["has_coeff"]), int(p["luma_mode"]), int(p["chroma_mode"]),
+                   tuple(int(v) for v in p["ref_frames"]),
+                   tuple((int(m[0]), int(m[1])) for m in p["mvs"]), int(r["tx_size"]),
+                   int(p["tx_type"]), int(p["sidx"]), (int(p["alpha_u"]), int(p["alpha_v"])))
+
+
+class ModeDecideResult(typing.NamedTuple):
+    decisions: np.ndarray   # MODE_DECISION [n]
+    cand_dist: np.ndarray   # u64 [n_cands]
+    cand_cost: np.ndarray   # f64 [n_cands]
+    cand_state: np.ndarray  # i32 [n_cands], MODE_STATE_*
+    rejected_blocks: int
+    rejected_cands: int
+
+    def decision(self, i) -> ModeDecision:
+        return ModeDecision.from_record(self.decisions[i])
+
+
+def segmentation_data(base_q_idx) -> np.ndarray:
+    """rv_segmentation_data: segmentation_optimize's ALT_Q deltas of the three
+    segments (src/segmentation.rs:29-48) as int16 [3]."""
+    out = np.zeros(3, np.int16)
+    _check_code(lib().rv_segmentation_data(int(base_q_idx), out.ctypes.data), "rv_segmentation_data")
+    return out
+
+
+def _importance_plane(who, importance, w_in_b, h_in_b):
+    if importance is None:
+        return None, 0
+    imp = np.ascontiguousarray(importance, np.float32)
+    if imp.ndim != 2 or imp.shape[1] < (int(w_in_b) + 1) // 2 or imp.shape[0] < (int(h_in_b) + 1) // 2:
+        err = Rav1eHipError(f"{who}: importance is [ceil(h_in_b / 2)][ceil(w_in_b / 2)] at least")
+        err.code = RV_EINVAL
+        raise err
+    return imp, imp.shape[1]
+
+
+def block_segments_batch(tiles, blocks, bsize, base_q_idx, w_in_b, h_in_b, importance=None,
+                         data=None):
+    """rv_block_segment_batch: per block of one bsize compute_mean_importance
+    (src/rdo.rs:477-493), the heuristic segment index of luma_chroma_mode_rdo
+    with quantizer_rdo off (:655-679) and get_qidx (src/encoder.rs:1061-1072).
+    blocks: MODE_BLOCK (tile, bo_x, bo_y); importance: fi.block_importances as
+    a 2-D float32 array, None: all zero; data: the ALT_Q deltas (default
+    segmentation_data(base_q_idx)).  Returns (sidx i32 [n], qindex i32 [n],
+    mean f32 [n], rejected)."""
+    who = "block_segments_batch"
+    tiles = np.ascontiguousarray(tiles, dtype=INTRA_TILE).reshape(-1)
+    blocks = np.ascontiguousarray(blocks, dtype=MODE_BLOCK).reshape(-1)
+    n = len(blocks)
+    dq = np.ascontiguousarray(segmentation_data(base_q_idx) if data is None else data, np.int16)
+    if dq.shape != (3,):
+        raise Rav1eHipError(f"{who}: data has three deltas")
+    imp, w_imp = _importance_plane(who, importance, w_in_b, h_in_b)
+    if int(bsize) < 0 or int(bsize) > 21 or int(bsize) > 12 or not 0 <= int(base_q_idx) <= 255 or \
+            int(w_in_b) < 1 or int(h_in_b) < 1:
+        # the library's own codes, without a device: nothing is allocated
+        _check_code(lib().rv_block_segment_batch(None, 0, None, 0, int(bsize), int(base_q_idx),
+                                                 dq.ctypes.data, None, w_imp, int(w_in_b), int(h_in_b),
+                                                 None, None, None, dq.ctypes.data, None),
+                    "rv_block_segment_batch")
+    dt, db, dst = DeviceBuffer.from_array(tiles), DeviceBuffer.from_array(blocks), DeviceBuffer(4)
+    di = DeviceBuffer.from_array(imp) if imp is not None else None
+    ds, dqi, dm = DeviceBuffer(4 * max(1, n)), DeviceBuffer(4 * max(1, n)), DeviceBuffer(4 * max(1, n))
+    _check_code(lib().rv_block_segment_batch(dt.ptr, len(tiles), db.ptr, n, int(bsize),
+                                             int(base_q_idx), dq.ctypes.data, di.ptr if di else None,
+                                             w_imp, int(w_in_b), int(h_in_b), ds.ptr, dqi.ptr, dm.ptr,
+                                             dst.ptr, None), "rv_block_segment_batch")
+    _sync(None)
+    return ds.download(np.int32, n), dqi.download(np.int32, n), dm.download(np.float32, n), \
+        int(dst.download(np.uint32)[0])
+
+
+def mode_decide_batch(src, cand_sets, tiles, blocks, cands, bsize, lambda_, dist_scale, w_in_b, h_in_b,
+                      importance=None, tune=Tune.Psnr, use_tx_domain_distortion=False,
+                      coeff_rate=True, bit_depth=8, tx_dist=None, tx_eob=None, seed=None, commit=None,
+                      lanes=0) -> ModeDecideResult:
+    """rv_mode_decide_batch: the end of rdo_mode_decision (src/rdo.rs:784-1259)
+    for n blocks of one bsize in one launch -- every candidate's
+    ScaledDistortion (compute_distortion :338-411 / compute_tx_distortion
+    :414-475) and compute_rd_cost (:563-568), the walk with the reference's
+    early-outs, the winner.  src: three DevicePlanes; cand_sets: the plane sets
+    a candidate's `set` indexes (as motion_compensate_batch's dsts); tiles
+    INTRA_TILE; blocks MODE_BLOCK; cands MODE_CAND in the reference's order of
+    evaluation; tx_dist (u64) / tx_eob (u32): the concatenated rows of
+    tx_blocks_batch's distortions and eobs that dist_off / eob_off index;
+    importance: fi.block_importances (2-D float32) or None; seed: MODE_DECISION
+    [n] to continue from (the CfL trial); commit: three DevicePlanes that
+    receive the winners' pixels.  Argument errors raise with the library's code
+    (Rav1eHipError.code) before anything is allocated on a device."""
+    who = "mode_decide_batch"
+    tiles = np.ascontiguousarray(tiles, dtype=INTRA_TILE).reshape(-1)
+    blocks = np.ascontiguousarray(blocks, dtype=MODE_BLOCK).reshape(-1)
+    cands = np.ascontiguousarray(cands, dtype=MODE_CAND).reshape(-1)
+    n, nc = len(blocks), len(cands)
+    for name, ps in (("src", src), ("commit", commit)):
+        if ps is not None and len(ps) < 3:
+            raise Rav1eHipError(f"{who}: {name} needs 3 planes")
+    sa = _plane_set(src, 3)
+    ca, ns = _plane_sets(who, cand_sets, 3)
+    ma = _plane_set(commit, 3)
+    imp, w_imp = _importance_plane(who, importance, w_in_b, h_in_b)
+    prm = RvModeDecideParams(int(bsize), int(bit_depth), int(tune), 1 if use_tx_domain_distortion else 0,
+                             1 if coeff_rate else 0, int(w_in_b), int(h_in_b), int(w_imp),
+                             float(lambda_))
+    for p in range(3):
+        prm.dist_scale[p] = float(dist_scale[p])
+    _check_code(lib().rv_mode_decide_check(sa, ca, ns, ma, C.byref(prm), 1 if imp is not None else 0,
+                                           int(lanes)), "rv_mode_decide_batch")
+    td = np.ascontiguousarray(tx_dist if tx_dist is not None else [], np.uint64).reshape(-1)
+    te = np.ascontiguousarray(tx_eob if tx_eob is not None else [], np.uint32).reshape(-1)
+    if len(td) != len(te):
+        raise Rav1eHipError(f"{who}: tx_dist and tx_eob have one entry per transform block each")
+    sd = None
+    if seed is not None:
+        sd = np.ascontiguousarray(seed, dtype=MODE_DECISION).reshape(-1)
+        if len(sd) != n:
+            raise Rav1eHipError(f"{who}: one seed per block")
+    dt, db, dc = DeviceBuffer.from_array(tiles), DeviceBuffer.from_array(blocks), \
+        DeviceBuffer.from_array(cands)
+    dd, de = DeviceBuffer.from_array(td), DeviceBuffer.from_array(te)
+    di = DeviceBuffer.from_array(imp) if imp is not None else None
+    dsd = DeviceBuffer.from_array(sd) if sd is not None else None
+    do = DeviceBuffer(MODE_DECISION.itemsize * max(1, n))
+    dcd, dcc, dcs = DeviceBuffer(8 * max(1, nc)), DeviceBuffer(8 * max(1, nc)), \
+        DeviceBuffer(4 * max(1, nc))
+    dst = DeviceBuffer(8)
+    _check_code(lib().rv_mode_decide_batch_lanes(
+        sa, ca, ns, ma, dt.ptr, len(tiles), db.ptr, n, dc.ptr, nc, dsd.ptr if dsd else None,
+        dd.ptr if len(td) else None, de.ptr if len(te) else None, len(td), di.ptr if di else None,
+        C.byref(prm), do.ptr, dcd.ptr, dcc.ptr, dcs.ptr, dst.ptr, int(lanes), None),
+        "rv_mode_decide_batch")
+    _sync(None)
+    st = dst.download(np.uint32, 2)
+    return ModeDecideResult(do.download(MODE_DECISION, n), dcd.download(np.uint64, nc),
+                            dcc.download(np.float64, nc), dcs.download(np.int32, nc), int(st[0]),
+                            int(st[1]))
 
 
 def prep_8tap_batch(src: DevicePlane, jobs, w, h, mode_x=0, mode_y=0, bit_depth=8):

@@ -6,21 +6,28 @@
 
 namespace rv {
 
-// compute_distortion_bias (src/rdo.rs:476-508) of the importance area of
-// m x m 4x4 blocks (BLOCK_8X8: m = 2; a chroma plane narrower than 8
-// pixels biases BLOCK_4X4 areas, m = 1) at 4x4-block (mi_x, mi_y) of the
-// frame: compute_mean_importance sums the f32 importances of the in-frame
-// 4x4 blocks in y-then-x order and divides by the full area; the bias is
-// (mean / 3) as f64 + 0.65.  imp: block_importances, w_imp per row, or null.
-__device__ __forceinline__ double distortion_bias(const float *imp, int w_imp, int w_in_b, int h_in_b,
-                                                  int mi_x, int mi_y, int m = 2) {
-  if (!imp) return 0.65;  // (0f32 / 3) as f64 + 0.65
-  const int x2 = mi_x + m < w_in_b ? mi_x + m : w_in_b;
-  const int y2 = mi_y + m < h_in_b ? mi_y + m : h_in_b;
+// compute_mean_importance (src/rdo.rs:477-493) of the importance area of
+// mw x mh 4x4 blocks at 4x4-block (mi_x, mi_y) of the frame: the f32
+// importances of the in-frame 4x4 blocks summed in y-then-x order, divided by
+// the full area.  imp: block_importances, w_imp per row, or null (all zero).
+__device__ __forceinline__ float mean_importance(const float *imp, int w_imp, int w_in_b, int h_in_b,
+                                                 int mi_x, int mi_y, int mw, int mh) {
+  if (!imp) return 0.f;
+  const int x2 = mi_x + mw < w_in_b ? mi_x + mw : w_in_b;
+  const int y2 = mi_y + mh < h_in_b ? mi_y + mh : h_in_b;
   float tot = 0.f;
   for (int y = mi_y; y < y2; y++)
     for (int x = mi_x; x < x2; x++) tot = __fadd_rn(tot, imp[(y >> 1) * w_imp + (x >> 1)]);
-  return (double)__fdiv_rn(__fdiv_rn(tot, (float)(m * m)), 3.0f) + 0.65;
+  return __fdiv_rn(tot, (float)(mw * mh));
+}
+// compute_distortion_bias (src/rdo.rs:495-508) of that area (BLOCK_8X8: mw =
+// mh = 2; a chroma plane narrower than 8 pixels biases BLOCK_4X4 areas, 1 x 1;
+// mh = 0: a square of mw): (mean / 3) as f64 + 0.65.
+__device__ __forceinline__ double distortion_bias(const float *imp, int w_imp, int w_in_b, int h_in_b,
+                                                  int mi_x, int mi_y, int mw = 2, int mh = 0) {
+  if (!imp) return 0.65;  // (0f32 / 3) as f64 + 0.65
+  const float mean = mean_importance(imp, w_imp, w_in_b, h_in_b, mi_x, mi_y, mw, mh ? mh : mw);
+  return (double)__fdiv_rn(mean, 3.0f) + 0.65;
 }
 // RawDistortion * bias (src/rdo.rs:539-544): `(value as f64 * bias) as u64`
 __device__ __forceinline__ uint64_t distortion_biased(uint64_t v, double bias) {
