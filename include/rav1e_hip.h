@@ -1426,6 +1426,93 @@ int rv_telescopic_subpel_batch(const rv_plane *org, const rv_plane *ref,
                                int bit_depth, rv_fs_result *d_out,
                                void *stream);
 
+/* ---- motion estimation of rdo_mode_decision (src/rdo.rs:858-878) ----------
+ * rv_motion_estimation_batch: DiamondSearch::motion_estimation (src/me.rs:
+ * 193-278, 391-463) for n blocks of one bsize x the sets.n_single single
+ * reference sets, one launch; d_me[n][n_single] is what
+ * rv_inter_mode_set_batch reads.  Item (b, i), all on the device:
+ *  - the reference plane is refs[3 * sets.slot[i]] (the table of
+ *    rv_motion_compensate_batch; only plane 0 of a set is read);
+ *  - pmv (rdo.rs:859-865): this_mv of entries 0 and 1 of d_stacks[b][i]
+ *    (d_stacks[n][n_single + compound] as rv_find_mvrefs_batch left it), zero
+ *    where the stack is shorter;
+ *  - d_cmv[b][i]: the caller's pmvs[ref_slot].unwrap_or_default() (rdo.rs:867);
+ *  - get_mv_range (me.rs:64-80) from the frame block offset (tile origin +
+ *    bo) and params.w_in_b / h_in_b; lambda = params.lambda, which the caller
+ *    forms as (fi.me_lambda * 256.0 * 0.5) as u32;
+ *  - get_subset_predictors (me.rs:82-174): zero, quantize_to_fullpel(cmv),
+ *    subsets A / B from d_tile_mvs[7][h_in_b][w_in_b] (ts.mvs[ref.to_index()],
+ *    frame-wide, read through the tile's rectangle: tile_mvs.cols() is the
+ *    tile's width in 4x4 units), subset C from d_prev_mvs[7][h_in_b][w_in_b]
+ *    (frame_mvs[ref.to_index()] of the frame in fi.ref_frames[0]'s slot, at
+ *    4x4 granularity; NULL: the slot is empty, no subset C);
+ *  - the full-pel diamond (me.rs:693-785, SAD, radius 16 -> 8), then the
+ *    sub-pel diamond from its winner (radius 4 -> 2, 1 under allow_hp; SATD
+ *    under use_satd, else SAD).  The SATD recost between them (me.rs:232-253)
+ *    is dead (get_best_predictor resets the cost, me.rs:663-664).
+ * d_res (may be NULL): [n][n_single], the MV and the final cost.  The motion
+ * fields are a snapshot the launch only reads: every item sees the same one,
+ * coding order is the caller's schedule (rv_save_block_motion_batch between
+ * launches).  The rule pmvs[ref_slot] = Some(b_me) of rdo.rs:872-876 is the
+ * caller's too.
+ * bsize 8x8 .. 64x64, squares, 2:1 and 1:2; 8 / 10 / 12 bit; any tiles
+ * (rv_intra_tile, pixels, a multiple of 4).
+ * RV_ENOTSUP, before any launch: 4xN / Nx4, 4:1 / 1:4, sizes above 64x64.
+ * RV_EINVAL, before any launch: null pointers, n < 0, a value that is no
+ * BlockSize, a sets value rv_inter_ref_sets_build could not have produced or
+ * whose slot is not in refs, n_refs outside 1..8, a bit depth other than
+ * 8 / 10 / 12 or one the planes' pixel type does not hold, subsampled planes,
+ * reference planes that differ in geometry, a source plane that does not hold
+ * the frame, a reference plane whose padding does not hold the furthest
+ * full-pel region (16 + w pixels beyond the frame on every side) or the
+ * furthest clamped sub-pel window.
+ * Rejected on the device, counted per item in d_status (cleared here), the
+ * item writing nothing: a tile index out of range, a tile that is not on 4x4
+ * units inside the frame, an offset that is negative, not a multiple of the
+ * block's size or leaves its tile (and with it the frame, where get_mv_range's
+ * usize subtraction would underflow), a stack length outside 0..9. */
+typedef struct rv_me_params {
+  int32_t bsize, bit_depth, use_satd, allow_hp;
+  int32_t w_in_b, h_in_b; /* fi.w_in_b / h_in_b: the frame in 4x4 units */
+  uint32_t lambda;
+  int32_t reserved;
+} rv_me_params;
+int rv_motion_estimation_batch(const rv_plane *org, const rv_plane *refs, int n_refs,
+                               const rv_intra_tile *d_tiles, int n_tiles,
+                               const rv_inter_blk *d_blocks, int n, rv_inter_ref_sets sets,
+                               const rv_mvref_result *d_stacks, const rv_mv *d_cmv,
+                               const rv_mv *d_tile_mvs, const rv_mv *d_prev_mvs,
+                               const rv_me_params *params, rv_mv *d_me, rv_fs_result *d_res,
+                               uint32_t *d_status, void *stream);
+
+/* rv_save_block_motion_batch: save_block_motion (src/encoder.rs:1432-1444) of
+ * a coding-order list into d_tile_mvs[7][h_in_b][w_in_b]: field ref_index gets
+ * mv over the job's bsize rectangle (any BlockSize) at (bo_x, bo_y) of its
+ * tile, clipped to the tile's mi_width / mi_height; where jobs overlap the
+ * later one in the array wins.  ref_index < 0 is skipped (an intra winner,
+ * src/encoder.rs:2171).  Rejected and counted in d_status (cleared here): a
+ * tile out of range or not on 4x4 units inside the frame, an offset that is
+ * negative or outside the tile, a value that is no BlockSize, ref_index above
+ * 6.  d_scratch: rv_save_block_motion_scratch_bytes bytes (0 for a frame
+ * outside 1..2^14 units).  RV_EINVAL before any launch: null pointers, n < 0
+ * or above 2^22, such a frame. */
+typedef struct rv_me_save_job {
+  int32_t tile, bo_x, bo_y; /* tile-relative 4x4 luma units */
+  int32_t bsize;
+  int32_t ref_index;        /* RefType::to_index(), 0 .. 6; < 0: skipped */
+  rv_mv mv;
+} rv_me_save_job;
+size_t rv_save_block_motion_scratch_bytes(int w_in_b, int h_in_b);
+int rv_save_block_motion_batch(const rv_me_save_job *d_jobs, int n, const rv_intra_tile *d_tiles,
+                               int n_tiles, int w_in_b, int h_in_b, rv_mv *d_tile_mvs,
+                               void *d_scratch, uint32_t *d_status, void *stream);
+
+/* pmv_idx of src/rdo.rs:1532-1536 / src/encoder.rs:2160-2166 (host): 0 above
+ * BLOCK_32X32, else ((bo_x & 32) >> 5) + ((bo_y & 32) >> 4) + 1 of the tile
+ * block offset; -1 for a value that is no BlockSize and for the 4:1 / 1:4
+ * sizes, on which the two sites disagree (enum order against greater_than). */
+int rv_me_pmv_index(int bsize, int bo_x, int bo_y);
+
 /* ---------------------------------------------------------------------
  * Hot-path replay driver (see DESIGN.md "Replay driver"): the per-frame
  * call structure of a speed-10 encode of a stream for the accelerated

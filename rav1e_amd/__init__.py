@@ -240,6 +240,13 @@ class RvInterMcParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("bsize", "filter_mode", "luma_only", "bit_depth")]
 
 
+class RvMeParams(C.Structure):
+    """rv_me_params (include/rav1e_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("bsize", "bit_depth", "use_satd", "allow_hp", "w_in_b",
+                                         "h_in_b")] + [("lambda_", C.c_uint32),
+                                                       ("reserved", C.c_int32)]
+
+
 def _declare(L):
     vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
     P = C.POINTER(RvPlane)
@@ -399,6 +406,11 @@ def _declare(L):
         "rv_motion_compensate_batch": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp]),
         "rv_motion_compensate_batch_lanes": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32,
                                                    vp]),
+        "rv_motion_estimation_batch": (i32, [vp, vp, i32, vp, i32, vp, i32, RvInterRefSets, vp, vp,
+                                             vp, vp, vp, vp, vp, vp, vp]),
+        "rv_save_block_motion_scratch_bytes": (C.c_size_t, [i32, i32]),
+        "rv_save_block_motion_batch": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "rv_me_pmv_index": (i32, [i32, i32, i32]),
         "rv_segmentation_data": (i32, [i32, vp]),
         "rv_block_segment_batch": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp,
                                          vp, vp]),
@@ -2526,7 +2538,8 @@ def inter_mode_set_batch(stacks, me, sets: RvInterRefSets, include_near_mvs=Fals
     every candidate's MVs for n blocks in one launch.  stacks: MVREF_RESULT
     (n, sets.n_sets) as find_mvrefs_batch wrote them per reference set (the
     compound query last); me: (n, sets.n_single, 2) int16 (row, col), the
-    searches' MVs; blocks: INTER_BLK [n] when the MC jobs are wanted.  Returns
+    searches' MVs, or the DeviceBuffer motion_estimation_batch(device=True)
+    returned; blocks: INTER_BLK [n] when the MC jobs are wanted.  Returns
     (lists INTER_LIST [n], mc_jobs INTER_MC_JOB (n, 20) or None, rejected):
     rejected blocks (a list above 20 entries, an empty compound stack: the
     reference panics on both) have n = 0 and no jobs."""
@@ -2535,9 +2548,14 @@ def inter_mode_set_batch(stacks, me, sets: RvInterRefSets, include_near_mvs=Fals
     ns, nsets = sets.n_single, sets.n_sets
     st = st.reshape(-1, nsets) if st.size else st.reshape(0, nsets)
     n = len(st)
-    mv = np.ascontiguousarray(me, np.int16)
-    if mv.size != n * ns * 2:
-        raise Rav1eHipError(f"{who}: me is (n, {ns}, 2) for {n} blocks")
+    if isinstance(me, DeviceBuffer):  # motion_estimation_batch(device=True): no host copy
+        if me.nbytes < n * ns * 4:
+            raise Rav1eHipError(f"{who}: the device me holds fewer than {n} x {ns} MVs")
+        mv = None
+    else:
+        mv = np.ascontiguousarray(me, np.int16)
+        if mv.size != n * ns * 2:
+            raise Rav1eHipError(f"{who}: me is (n, {ns}, 2) for {n} blocks")
     lists = np.zeros(n, INTER_LIST)
     blk = None
     if blocks is not None:
@@ -2546,7 +2564,7 @@ def inter_mode_set_batch(stacks, me, sets: RvInterRefSets, include_near_mvs=Fals
             raise Rav1eHipError(f"{who}: one INTER_BLK per block")
     if n == 0:
         return lists, (np.zeros((0, INTER_MAX_CANDS), INTER_MC_JOB) if blk is not None else None), 0
-    ds, dm, dl, dst = DeviceBuffer.from_array(st), DeviceBuffer.from_array(mv), \
+    ds, dm, dl, dst = DeviceBuffer.from_array(st), me if mv is None else DeviceBuffer.from_array(mv), \
         DeviceBuffer(lists.nbytes), DeviceBuffer(4)
     db = DeviceBuffer.from_array(blk) if blk is not None else None
     dj = DeviceBuffer(n * INTER_MAX_CANDS * INTER_MC_JOB.itemsize) if blk is not None else None
@@ -2601,6 +2619,130 @@ def motion_compensate_batch(refs, dsts, tiles, jobs, bsize, filter_mode=FilterMo
                 "rv_motion_compensate_batch")
     _sync(None)
     return int(dst.download(np.uint32)[0])
+
+
+# ---- motion estimation of rdo_mode_decision (rv_motion_est.hip) -------------
+ME_SAVE_JOB = np.dtype([("tile", "<i4"), ("bo_x", "<i4"), ("bo_y", "<i4"), ("bsize", "<i4"),
+                        ("ref_index", "<i4"), ("mv", "<i2", 2)])  # rv_me_save_job
+
+
+def me_lambda_u32(me_lambda) -> int:
+    """(fi.me_lambda * 256.0 * 0.5) as u32 (src/me.rs:207), formed in f64; `as`
+    truncates and saturates."""
+    v = float(me_lambda) * 256.0 * 0.5
+    if not v > 0.0:  # NaN and negatives
+        return 0
+    return min(int(v), 0xFFFFFFFF)
+
+
+def me_pmv_index(bsize, bo_x, bo_y) -> int:
+    """rv_me_pmv_index: pmv_idx of src/rdo.rs:1532-1536 / src/encoder.rs:
+    2160-2166 for the block at tile block offset (bo_x, bo_y): 0 above 32x32,
+    else ((bo_x & 32) >> 5) + ((bo_y & 32) >> 4) + 1."""
+    r = lib().rv_me_pmv_index(int(bsize), int(bo_x), int(bo_y))
+    if r < 0:
+        raise Rav1eHipError("me_pmv_index: no BlockSize, or a 4:1 / 1:4 size")
+    return r
+
+
+def _me_field(who, a, w_in_b, h_in_b):
+    """A motion field [7][h_in_b][w_in_b] of (row, col) on the device."""
+    if isinstance(a, DeviceBuffer):
+        if a.nbytes < 7 * h_in_b * w_in_b * 4:
+            raise Rav1eHipError(f"{who}: a device field holds fewer than 7 x {h_in_b} x {w_in_b} MVs")
+        return a
+    a = np.ascontiguousarray(a, np.int16)
+    if a.shape != (7, h_in_b, w_in_b, 2):
+        raise Rav1eHipError(f"{who}: a field is (7, {h_in_b}, {w_in_b}, 2) int16, got {a.shape}")
+    return DeviceBuffer.from_array(a)
+
+
+def motion_estimation_batch(org: DevicePlane, refs, tiles, blocks, sets: RvInterRefSets, stacks,
+                            cmv, tile_mvs, prev_mvs, bsize, w_in_b, h_in_b, lambda_,
+                            use_satd=True, allow_hp=False, bit_depth=8, device=False):
+    """rv_motion_estimation_batch: DiamondSearch::motion_estimation (src/me.rs:
+    193-278) of rdo_mode_decision (src/rdo.rs:858-878) for n blocks of one bsize
+    x the sets.n_single single reference sets, in one launch: pmv pair from the
+    stacks, MV range, get_subset_predictors, the full-pel and the sub-pel
+    diamond, all on the device.
+
+    org: the source luma DevicePlane; refs: the reference plane sets of
+    motion_compensate_batch (set sets.slot[i] is searched for single set i,
+    plane 0 only); tiles INTRA_TILE; blocks INTER_BLK [n]; stacks MVREF_RESULT
+    (n, sets.n_sets) as find_mvrefs_batch wrote them, or a DeviceBuffer of
+    them; cmv (n, n_single, 2) int16 (row, col): pmvs[ref_slot]
+    .unwrap_or_default() (rdo.rs:867); tile_mvs / prev_mvs: (7, h_in_b, w_in_b,
+    2) int16 fields (ts.mvs, and frame_mvs of the frame in fi.ref_frames[0]'s
+    slot) or DeviceBuffers; prev_mvs None: that slot is empty.  lambda_:
+    me_lambda_u32(fi.me_lambda).
+
+    The fields are a snapshot: every item of the batch reads the same one.
+    Coding order is the caller's schedule, and so is the rule of
+    rdo.rs:872-876: after the search of a 32x32 or 64x64 block (and not under
+    encode_bottomup) the caller sets pmvs[ref_slot] = Some(b_me), which the
+    cmv of later calls must carry.
+
+    Returns (me, res, rejected): me (n, n_single, 2) int16, or with
+    device=True the DeviceBuffer inter_mode_set_batch takes as it is; res
+    FS_RESULT (n, n_single) (the MV and the final cost); rejected items (a bad
+    tile, offset or stack length) write nothing and leave zeros."""
+    who = "motion_estimation_batch"
+    tiles = np.ascontiguousarray(tiles, dtype=INTRA_TILE).reshape(-1)
+    blk = np.ascontiguousarray(blocks, INTER_BLK).reshape(-1)
+    n, ns, nsets = len(blk), sets.n_single, sets.n_sets
+    ra, nr = _plane_sets(who, refs, 1)
+    if nr == 0:
+        raise Rav1eHipError(f"{who}: at least one reference set")
+    if isinstance(stacks, DeviceBuffer):
+        dstk = stacks
+        if dstk.nbytes < n * nsets * MVREF_RESULT.itemsize:
+            raise Rav1eHipError(f"{who}: the device stacks hold fewer than {n} x {nsets} records")
+    else:
+        st = np.ascontiguousarray(stacks, MVREF_RESULT)
+        if st.size != n * nsets:
+            raise Rav1eHipError(f"{who}: stacks is (n, {nsets}) for {n} blocks")
+        dstk = DeviceBuffer.from_array(st)
+    cm = np.ascontiguousarray(cmv, np.int16)
+    if cm.size != n * ns * 2:
+        raise Rav1eHipError(f"{who}: cmv is (n, {ns}, 2) for {n} blocks")
+    dtm = _me_field(who, tile_mvs, w_in_b, h_in_b)
+    dpm = _me_field(who, prev_mvs, w_in_b, h_in_b) if prev_mvs is not None else None
+    prm = RvMeParams(int(bsize), int(bit_depth), 1 if use_satd else 0, 1 if allow_hp else 0,
+                     int(w_in_b), int(h_in_b), int(lambda_), 0)
+    dt, db, dc = DeviceBuffer.from_array(tiles), DeviceBuffer.from_array(blk), \
+        DeviceBuffer.from_array(cm)
+    dme, dres, dst = DeviceBuffer(n * ns * 4), DeviceBuffer(n * ns * 16), DeviceBuffer(4)
+    dme.zero()
+    dres.zero()
+    _check_code(lib().rv_motion_estimation_batch(
+        C.byref(org.desc), ra, nr, dt.ptr, len(tiles), db.ptr, n, sets, dstk.ptr, dc.ptr, dtm.ptr,
+        dpm.ptr if dpm else None, C.byref(prm), dme.ptr, dres.ptr, dst.ptr, None),
+        "rv_motion_estimation_batch")
+    _sync(None)
+    res = dres.download(FS_RESULT, n * ns).reshape(n, ns)
+    me = dme if device else dme.download(np.int16, n * ns * 2).reshape(n, ns, 2)
+    return me, res, int(dst.download(np.uint32)[0])
+
+
+def save_block_motion_batch(jobs, tiles, tile_mvs, w_in_b, h_in_b):
+    """rv_save_block_motion_batch: save_block_motion (src/encoder.rs:1432-1444)
+    of a coding-order ME_SAVE_JOB list (tile, tile block offset, bsize,
+    ref_index = RefType.to_index(), mv (row, col)) into the field tile_mvs
+    ((7, h_in_b, w_in_b, 2) int16, or a DeviceBuffer that is updated in place):
+    each rectangle clipped to its tile's mi_width / mi_height, a later job
+    winning over an earlier one, ref_index < 0 (an intra winner) skipped.
+    Returns (the field's DeviceBuffer, rejected)."""
+    who = "save_block_motion_batch"
+    tiles = np.ascontiguousarray(tiles, dtype=INTRA_TILE).reshape(-1)
+    jobs = np.ascontiguousarray(jobs, ME_SAVE_JOB).reshape(-1)
+    dtm = _me_field(who, tile_mvs, w_in_b, h_in_b)
+    scr = DeviceBuffer(lib().rv_save_block_motion_scratch_bytes(int(w_in_b), int(h_in_b)))
+    dj, dt, dst = DeviceBuffer.from_array(jobs), DeviceBuffer.from_array(tiles), DeviceBuffer(4)
+    _check_code(lib().rv_save_block_motion_batch(dj.ptr, len(jobs), dt.ptr, len(tiles), int(w_in_b),
+                                                 int(h_in_b), dtm.ptr, scr.ptr, dst.ptr, None),
+                "rv_save_block_motion_batch")
+    _sync(None)
+    return dtm, int(dst.download(np.uint32)[0])
 
 
 # ---- a block's mode decision (rv_mode_decide.hip) ---------------------------

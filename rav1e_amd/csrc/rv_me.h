@@ -6,6 +6,17 @@
 #include "rv_chain.h"
 #include "rv_device.h"
 
+namespace rv {
+// get_mv_rate's diff_to_rate (src/me.rs:1006-1021), shared by the diamond
+// searches of rv_me_diamond.hip and rv_motion_est.hip
+__device__ __forceinline__ uint32_t ds_diff_to_rate(int16_t diff, int hp) {
+  int16_t d = hp ? diff : (int16_t)(diff >> 1);
+  if (d == 0) return 0;
+  uint32_t a = (uint16_t)(d < 0 ? -d : d);
+  return 2u * (16u - (uint32_t)(__builtin_clz(a) - 16));
+}
+}  // namespace rv
+
 // rv_me.hip
 int rv_full_search_multi(const rv_plane *org, const rv_plane *refs, int n_refs,
                          const rv_fs_job *d_jobs, int n_per_ref, int blk_w, int blk_h,

@@ -56,14 +56,6 @@ __constant__ int8_t kReg[2][16][8] = {
      {0, 0, -8, 38, 110, -12, 0, 0}, {0, 0, -6, 28, 116, -10, 0, 0},
      {0, 0, -4, 18, 122, -8, 0, 0}, {0, 0, -2, 8, 126, -4, 0, 0}}};
 
-// get_mv_rate's diff_to_rate (src/me.rs:1006-1021)
-__device__ __forceinline__ uint32_t ds_diff_to_rate(int16_t diff, int hp) {
-  int16_t d = hp ? diff : (int16_t)(diff >> 1);
-  if (d == 0) return 0;
-  uint32_t a = (uint16_t)(d < 0 ? -d : d);
-  return 2u * (16u - (uint32_t)(__builtin_clz(a) - 16));
-}
-
 // compute_mv_rd_cost (src/me.rs:840-856) given the distortion
 __device__ __forceinline__ uint64_t ds_cost(uint32_t dist, rv_mv mv, const rv_ds_job &jb,
                                             int hp) {
